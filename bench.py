@@ -97,8 +97,41 @@ def parse():
     ap.add_argument("--no-cfg4-annex", action="store_true", help="N > 1: skip the temporal_shard_cfg4 strong-scaling annex")
     ap.add_argument("--cpu-baseline-wall", type=float, default=420.0,
                     help="wall-time guard (s) of the in-run full-size CPU baseline; beyond it the kept measurement is reported")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32), at most 64 MB in "
+                         "all: beyond that every output is written as the same fixed, seeded sample of its elements (dump_outputs)")
     ap.add_argument("--cpu-baseline-worker", nargs=4, metavar=("FAMILY", "T", "H", "W"), default=None, help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6 - (1 << 16)  # --dump-outputs: 64 MB in all, less room for the .npy headers
+
+
+def dump_outputs(dirpath, named, budget=DUMP_BUDGET_BYTES, seed=0):
+    """write every (name, tensor) of `named` as dirpath/<name>.npy -- float64 stays float64, every other dtype becomes float32.  When
+    they hold more than `budget` bytes in all, each keeps the same fraction of its elements: the sorted flat indices drawn from a
+    generator seeded with `seed`, which depend on the shapes alone, so two builds run with the same arguments are compared element
+    for element.  Returns {name: [shape, elements written]}."""
+    import numpy as np
+    import torch
+
+    named = [(n, t) for n, t in named if t is not None]
+    total = sum(t.numel() * (8 if t.dtype == torch.float64 else 4) for _, t in named)
+    frac = min(1.0, budget / total) if total else 1.0
+    os.makedirs(dirpath, exist_ok=True)
+    written = {}
+    for n, t in named:
+        flat = t.detach().reshape(-1)
+        if frac < 1.0:
+            idx = torch.randint(flat.numel(), (int(flat.numel() * frac),), generator=torch.Generator().manual_seed(seed))
+            flat = flat[idx.sort().values.to(flat.device)]
+        a = flat.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(dirpath, n + ".npy"), a if frac < 1.0 else a.reshape(tuple(t.shape)))
+        written[n] = [list(t.shape), int(a.size)]
+    return written
 
 
 def self_launch(args) -> int:
@@ -533,24 +566,29 @@ def main():
         g = torch.Generator().manual_seed(1000 + (0 if cfg4 else rank))
         x = (torch.rand((B, 3, T, H, W), generator=g) * 2 - 1).to(dtype).cuda()
 
+    # every step returns what a caller of the timed path receives, named by `outputs` (--dump-outputs); the last one is the pixels
     if tshard:
+        outputs = ("moments", "recon_local")
         def step():
             return temporal_shard_step(vae, x, T)
     elif cfg4 and dist is not None:
+        outputs = ("moments", "recon_local")
         def step():
             # (window x spatial tile) network calls split over the ranks (8 x 6 = 48 units at cfg 4: one window per rank on 8 GPUs,
             # no tile traffic; fewer windows than ranks -> the tiles of a window spread out, raw tiles go point-to-point to the
             # rank that blends the window)
             mom = D.encode_units_sharded(vae, x)                       # all_gather of the latents (15 MB)
             z = mom[:, :mom.shape[1] // 2]
-            return D.decode_units_sharded(vae, z, gather=False)        # pixels stay sharded (713 MB if gathered)
+            return mom, D.decode_units_sharded(vae, z, gather=False)   # pixels stay sharded (713 MB if gathered)
     elif cfg5:
+        outputs = ("latents",)
         def step():
-            return vae.encode_latents(x, sample=False)                 # the latent pre-compute API
+            return (vae.encode_latents(x, sample=False),)              # the latent pre-compute API
     else:
+        outputs = ("latents", "recon")
         def step():
             z = vae.encode(x).latent_dist.mode()
-            return vae.decode(z).sample
+            return z, vae.decode(z).sample
 
     for _ in range(args.warmup):
         step()
@@ -561,12 +599,13 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        y = step()
+        last = step()
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    y = last[-1]
     assert tshard or cfg5 or (cfg4 and dist is not None) or y.shape == x.shape
     rank_times = None
     traffic = None
@@ -578,6 +617,11 @@ def main():
         traffic = {"bytes_sent_per_step_by_rank": [int(v[1].item()) // max(args.steps, 1) for v in ts],
                    "bytes_recv_per_step_by_rank": [int(v[2].item()) // max(args.steps, 1) for v in ts]}
         elapsed = max(float(v[0].item()) for v in ts)
+    if args.dump_outputs:
+        sfx = f"_rank{rank}" if world > 1 else ""
+        dumped = dump_outputs(args.dump_outputs, [(n + sfx, t) for n, t in zip(outputs, last)], DUMP_BUDGET_BYTES // world)
+        print(f"bench.py: outputs of the last timed step in {args.dump_outputs}: {json.dumps(dumped)}", file=sys.stderr)
+    del last, y
 
     strong = cfg4                                 # one fixed clip split over the ranks; everything else: per-rank work fixed
     if tshard:

@@ -79,6 +79,41 @@ GRAD_CASES = {
 }
 
 
+# fixtures that stand in for the reference's modules in the CPU tests (oracle/make_golden.py pins):
+#   PIN_FIXTURE:    the reference's encode moments / decode(mode()) recon of PIN_CASES (weight seed PIN_WSEED, input seed PIN_XSEED),
+#                   keys "<pin_key>_moments" / "<pin_key>_recon"          (tests/test_oracle_vs_reference.py)
+#   TILING_FIXTURE: the reference's wrapper around the test doubles of tests/test_host_logic.py, for both families and its first
+#                   three CFGS on TILING_SHAPE (torch.rand, seed 1); identical results are stored once: "case_<family>_<cfg index>"
+#                   names the index k of "enc_<k>_*" / "dec_<k>_*", each result kept as its shape, tensor_digest and the elements
+#                   at sample_index (the full results are 53 MB of float32: the digest pins every bit of them)   (tests/test_host_logic.py)
+#   TABLES_FIXTURE: the reference's state-dict key -> shape tables and model configs (tests/test_state_dict_contract.py,
+#                   tests/test_engine_host_logic.py)
+PIN_CASES = [("sd3", (1, 3, 5, 32, 32)), ("vae3d", (1, 3, 5, 32, 32)), ("sd3", (2, 3, 1, 32, 48)), ("vae3d", (1, 3, 21, 32, 32))]
+PIN_WSEED, PIN_XSEED = 5, 9
+PIN_FIXTURE = "ref_oracle_pins"
+TILING_SHAPE = (1, 3, 33, 200, 328)
+TILING_FIXTURE = "ref_tiling_wrapper"
+TABLES_FIXTURE = "ref_module_tables"
+
+
+def pin_key(family: str, shape) -> str:
+    return family + "_" + "x".join(str(v) for v in shape)
+
+
+def tensor_digest(t) -> str:
+    """sha256 of a float32 tensor's values in row-major order, -0.0 counted as 0.0: equal digests <=> torch.equal for finite tensors"""
+    import hashlib
+
+    import torch
+    return hashlib.sha256((t.detach().to(torch.float32) + 0.0).contiguous().numpy().tobytes()).hexdigest()
+
+
+def sample_index(numel: int, n: int = 1024, seed: int = 0):
+    """the flat indices of a stored result's sample: n seeded ones (sorted)"""
+    import torch
+    return torch.randint(0, numel, (n,), generator=torch.Generator().manual_seed(seed)).sort().values
+
+
 def grad_sample_index(name: str, numel: int, n: int = 4096):
     """the flat indices of parameter `name`'s stored gradient sample: all of them for tensors of <= n elements, else n seeded ones"""
     import zlib

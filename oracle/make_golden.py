@@ -268,8 +268,80 @@ def main_grad(only=None):
         np.savez_compressed(os.path.join(out_dir, name + ".npz"), **out)
 
 
+def main_pins():
+    """fixtures that let the CPU tests check the oracle, the wrapper's host logic and the state-dict tables against the reference's
+    own modules without importing them (golden_cases PIN_FIXTURE / TILING_FIXTURE / TABLES_FIXTURE)"""
+    import json
+
+    from oracle.golden_cases import (CONSTRAINT_CFG, LDM_CFG, PIN_CASES, PIN_FIXTURE, PIN_WSEED, PIN_XSEED, TABLES_FIXTURE,
+                                     TILING_FIXTURE, TILING_SHAPE, pin_key, sample_index, tensor_digest)
+    from oracle.ref_loader import load_reference_constraint, load_reference_ldm
+
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    from test_host_logic import CFGS, StubDec, StubEnc
+
+    ref = load_reference()
+    torch.set_grad_enabled(False)
+    out_dir = os.path.join(os.path.dirname(HERE), "tests", "golden")
+
+    def cls_of(family):
+        return ref.CVVAESD3Model if family == "sd3" else ref.CVVAEModel
+
+    pins = {}
+    for family, shape in PIN_CASES:
+        model = cls_of(family)().eval()
+        sd = seeded_state_dict({k: v.shape for k, v in model.state_dict().items()}, PIN_WSEED)
+        model.load_state_dict(sd, strict=True)
+        post = model.encode(seeded_input(shape, PIN_XSEED)).latent_dist
+        pins[pin_key(family, shape) + "_moments"] = post.parameters.numpy().astype(np.float32)
+        pins[pin_key(family, shape) + "_recon"] = model.decode(post.mode()).sample.numpy().astype(np.float32)
+    np.savez_compressed(os.path.join(out_dir, PIN_FIXTURE + ".npz"), **pins)
+    print(f"{PIN_FIXTURE}: {sorted(pins)}")
+
+    tiling, uniq = {}, []
+    for family in ("sd3", "vae3d"):
+        for i, cfg in enumerate(CFGS[:3]):
+            with torch.device("meta"):
+                r = cls_of(family)(**cfg)
+            r.encoder, r.decoder = StubEnc(), StubDec()
+            x = torch.rand(TILING_SHAPE, generator=torch.Generator().manual_seed(1)) * 2 - 1
+            enc = r.encode(x).latent_dist.parameters
+            dec = r.decode(enc[:, :4]).sample
+            k = next((j for j, (e, d) in enumerate(uniq) if torch.equal(e, enc) and torch.equal(d, dec)), None)
+            if k is None:
+                k = len(uniq)
+                uniq.append((enc, dec))
+                for part, t in (("enc", enc), ("dec", dec)):
+                    tiling[f"{part}_{k}_shape"] = np.asarray(t.shape, dtype=np.int64)
+                    tiling[f"{part}_{k}_digest"] = np.asarray(tensor_digest(t))
+                    tiling[f"{part}_{k}_sample"] = t.reshape(-1)[sample_index(t.numel())].numpy()
+            tiling[f"case_{family}_{i}"] = np.int64(k)
+    np.savez_compressed(os.path.join(out_dir, TILING_FIXTURE + ".npz"), **tiling)
+    print(f"{TILING_FIXTURE}: {len(uniq)} distinct results of {2 * 3} cases")
+
+    def shapes(m):
+        return {k: list(v.shape) for k, v in m.state_dict().items()}
+
+    tables = {"state_dict": {}, "config": {}}
+    for family in ("sd3", "vae3d"):
+        with torch.device("meta"):
+            m = cls_of(family)()
+        tables["state_dict"][family], tables["config"][family] = shapes(m), dict(m.config)
+    with torch.device("meta"):
+        tables["constraint2d"] = shapes(load_reference_constraint().DecoderWith3DWrapper(**CONSTRAINT_CFG))
+    ldm = load_reference_ldm()
+    tables["ldm2d_encoder"] = shapes(ldm.EncoderWith3DWrapper(**LDM_CFG))
+    tables["ldm2d_decoder"] = shapes(ldm.DecoderWith3DWrapper(**LDM_CFG))
+    with open(os.path.join(out_dir, TABLES_FIXTURE + ".json"), "w") as f:
+        json.dump(tables, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(f"{TABLES_FIXTURE}: {sorted(tables)}")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "grad":
+    if len(sys.argv) > 1 and sys.argv[1] == "pins":
+        main_pins()
+    elif len(sys.argv) > 1 and sys.argv[1] == "grad":
         main_grad(sys.argv[2:])
     elif len(sys.argv) > 1 and sys.argv[1] == "dec":
         main_dec(sys.argv[2:])

@@ -1,8 +1,8 @@
 """State-dict key -> shape tables for both families, derived from the config alone (no module
 construction).  TEST INFRASTRUCTURE: lets the oracle/golden tests build seeded weights without the
 reference or the product.  Key names follow the reference's on-disk contract;
-tests/test_state_dict_contract.py checks them against the product's modules and, when /root/reference
-is present, against the reference's own state_dict()."""
+tests/test_state_dict_contract.py checks them against the product's modules and against the reference's own
+state_dict() as stored in tests/golden/ref_module_tables.json."""
 
 
 def _conv(d, pre, co, ci, k):

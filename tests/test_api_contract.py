@@ -147,3 +147,32 @@ def test_bench_helpers():
     assert bench.time_groups(0, 1, 1, 1, False, False) == 1
     src = open(bench.__file__).read()
     assert "torch.distributed.run" in src and "--nproc-per-node" in src
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 arrays (float64 kept) in full under the budget; over it, the same seeded sample of every
+    output's elements from run to run, within the budget.  --steps below 1 is refused."""
+    import numpy as np
+
+    import bench
+    g = torch.Generator().manual_seed(0)
+    lat, rec, f64 = torch.randn(2, 4, 3, generator=g).bfloat16(), torch.randn(3, 50, 40, generator=g), torch.randn(7, dtype=torch.float64)
+    got = bench.dump_outputs(str(tmp_path / "full"), [("latents", lat), ("recon", rec), ("stats", f64), ("none", None)])
+    assert got == {"latents": [[2, 4, 3], 24], "recon": [[3, 50, 40], 6000], "stats": [[7], 7]}
+    a = np.load(tmp_path / "full" / "latents.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, lat.float().numpy())
+    assert np.array_equal(np.load(tmp_path / "full" / "recon.npy"), rec.numpy())
+    assert np.load(tmp_path / "full" / "stats.npy").dtype == np.float64
+    budget = 4 * 1000
+    for d in ("s1", "s2"):
+        got = bench.dump_outputs(str(tmp_path / d), [("latents", lat), ("recon", rec)], budget)
+        assert 4 * sum(n for _, n in got.values()) <= budget and got["recon"] == [[3, 50, 40], int(6000 * budget / 4 / 6024)]
+    for n in ("latents", "recon"):
+        s1, s2 = np.load(tmp_path / "s1" / (n + ".npy")), np.load(tmp_path / "s2" / (n + ".npy"))
+        assert s1.dtype == np.float32 and s1.ndim == 1 and np.array_equal(s1, s2)
+    assert np.isin(np.load(tmp_path / "s1" / "recon.npy"), rec.numpy()).all()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "3", "--dump-outputs", str(tmp_path)])
+    assert bench.parse().steps == 3
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()

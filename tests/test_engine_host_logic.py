@@ -212,19 +212,20 @@ def test_ldm_2d_wrappers_match_reference_golden_through_emulated_kernels(name, g
     assert np.abs(out.numpy() - gold["out"]).max() <= TOL
 
 
-def test_ldm_2d_wrappers_import_path_and_state_dict():
-    """the reference's module path and, when it is mounted, its classes' state-dict names and shapes"""
+def test_ldm_2d_wrappers_import_path_and_state_dict(golden_dir):
+    """the reference's module path and its classes' state-dict names and shapes (tests/golden/ref_module_tables.json)"""
+    import json
+
     from lvdm.modules.diffusionmodules.model import DecoderWith3DWrapper, EncoderWith3DWrapper
-    from oracle.golden_cases import LDM_CFG
-    from oracle.ref_loader import load_reference_ldm, reference_available
+    from oracle.golden_cases import LDM_CFG, TABLES_FIXTURE
     e, d = EncoderWith3DWrapper(**LDM_CFG), DecoderWith3DWrapper(**LDM_CFG)
     assert len(e.state_dict()) == 108 and len(d.state_dict()) == 140
     assert "quant_conv.weight" in e.state_dict() and "post_quant_conv.weight" in d.state_dict()
     assert "quant_conv.weight" not in EncoderWith3DWrapper(legacy=False, **LDM_CFG).state_dict()
-    if reference_available():
-        ref = load_reference_ldm()
-        for mine, theirs in ((e, ref.EncoderWith3DWrapper(**LDM_CFG)), (d, ref.DecoderWith3DWrapper(**LDM_CFG))):
-            assert {k: tuple(v.shape) for k, v in mine.state_dict().items()} == {k: tuple(v.shape) for k, v in theirs.state_dict().items()}
+    with open(os.path.join(golden_dir, TABLES_FIXTURE + ".json")) as f:
+        ref = json.load(f)
+    for mine, theirs in ((e, ref["ldm2d_encoder"]), (d, ref["ldm2d_decoder"])):
+        assert {k: tuple(v.shape) for k, v in mine.state_dict().items()} == {k: tuple(v) for k, v in theirs.items()}
     with pytest.raises(NotImplementedError):
         EncoderWith3DWrapper(**dict(LDM_CFG, attn_resolutions=[32]))
 

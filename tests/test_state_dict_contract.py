@@ -1,10 +1,19 @@
 """The on-disk contract: the product's state_dict keys/shapes must equal the reference's.
-oracle/shapes.py is the travelling copy of that table; when /root/reference is present it is re-derived live."""
+oracle/shapes.py is the travelling copy of that table; tests/golden/ref_module_tables.json holds the reference's own tables and
+configs as its modules report them (python -m oracle.make_golden pins)."""
+import json
+import os
+
 import pytest
 import torch
 
-from oracle.ref_loader import load_reference, reference_available
+from oracle.golden_cases import TABLES_FIXTURE
 from oracle.shapes import state_dict_shapes
+
+
+def reference_tables(golden_dir):
+    with open(os.path.join(golden_dir, TABLES_FIXTURE + ".json")) as f:
+        return json.load(f)
 
 
 def _product(family, **cfg):
@@ -21,17 +30,13 @@ def test_product_keys_match_table(family):
     assert len(got) == (244 if family == "sd3" else 254)  # SURVEY.md 8b [probe]
 
 
-@pytest.mark.skipif(not reference_available(), reason="/root/reference not mounted (GPU box)")
 @pytest.mark.parametrize("family", ["sd3", "vae3d"])
-def test_table_matches_reference(family):
-    ref = load_reference()
-    cls = ref.CVVAESD3Model if family == "sd3" else ref.CVVAEModel
-    with torch.device("meta"):
-        m = cls()
-    assert {k: tuple(v.shape) for k, v in m.state_dict().items()} == state_dict_shapes(family)
+def test_table_matches_reference(family, golden_dir):
+    ref = reference_tables(golden_dir)
+    assert {k: tuple(v) for k, v in ref["state_dict"][family].items()} == state_dict_shapes(family)
     # config keys and defaults (modeling_vae.py:26-50 / 350-380)
     mine = _product(family).config.to_dict()
-    theirs = dict(m.config)
+    theirs = ref["config"][family]
     assert set(mine) == set(theirs)
     for k in theirs:
         assert mine[k] == theirs[k], k
@@ -57,22 +62,18 @@ def test_no_cpu_fallback():
         m.encoder(torch.zeros(1, 3, 1, 32, 32))
 
 
-def test_constraint_decoder_keys_match_table_and_reference():
+def test_constraint_decoder_keys_match_table_and_reference(golden_dir):
     """the frozen 2-D constraint decoder, instantiated through the reference's module path with the yaml's
-    params (configs/cvvae_sd3_constraint_training.yaml:40-51): same state-dict keys and shapes as the table, and -- when the
-    reference is mounted -- as the reference's own DecoderWith3DWrapper; unsupported configurations fail at construction."""
+    params (configs/cvvae_sd3_constraint_training.yaml:40-51): same state-dict keys and shapes as the table and as the
+    reference's own DecoderWith3DWrapper; unsupported configurations fail at construction."""
     from lvdm.modules.diffusionmodules.vae_models_sd3 import DecoderWith3DWrapper
     from oracle.golden_cases import CONSTRAINT_CFG
-    from oracle.ref_loader import load_reference_constraint
     from oracle.shapes import constraint2d_shapes
 
     m = DecoderWith3DWrapper(**CONSTRAINT_CFG)
     got = {k: tuple(v.shape) for k, v in m.state_dict().items()}
     assert got == constraint2d_shapes(CONSTRAINT_CFG) and len(got) == 138
-    if reference_available():
-        with torch.device("meta"):
-            r = load_reference_constraint().DecoderWith3DWrapper(**CONSTRAINT_CFG)
-        assert {k: tuple(v.shape) for k, v in r.state_dict().items()} == got
+    assert {k: tuple(v) for k, v in reference_tables(golden_dir)["constraint2d"].items()} == got
     with pytest.raises(NotImplementedError):
         DecoderWith3DWrapper(**dict(CONSTRAINT_CFG, norm_type="spatial"))
     with pytest.raises(RuntimeError, match="no CPU fallback"):
