@@ -11,21 +11,28 @@ N > 1: one process per GPU over RCCL.  `python bench.py --gpus N` launches the N
 shard: ONE clip of 1 + 16 N frames at 512x512 whose frames arrive SHARDED ON TIME (rank r holds only its own 16 -- rank 0: 17 --
 frames), the causal halo frame exchanged point-to-point over RCCL (`batch_isend_irecv`), every rank coding its own 17-frame
 window, the latents all-gathered, the pixels left sharded (cvvae_amd/dist.py `codec_step_time_sharded`; weak scaling: the
-per-GPU work is cfg 3's window whatever N is, and at N = 1 the step IS cfg 3).  After the timed region every rank checks its
-slice bit for bit against the single-process wrapper run on the whole clip.  Annex `temporal_shard_cfg4` (N > 1): BASELINE cfg 4
-(T = 129, 720x1280) time-sharded the same way -- strong scaling, with the single-process time measured in the same invocation.
+per-GPU work is cfg 3's window whatever N is, and at N = 1 the step IS cfg 3).  With --full, after the timed region every rank
+checks its slice bit for bit against the single-process wrapper run on the whole clip, and annex `temporal_shard_cfg4` (N > 1) runs
+BASELINE cfg 4 (T = 129, 720x1280) time-sharded the same way -- strong scaling, with the single-process time measured in the same
+invocation.
 `--workload cfg3_sd3_T17_512` (or cfg2 / cfg5) at N > 1 keeps the older independent-clips mode (no data-path collective).
 value = frames of all ranks / max-over-ranks time.
 
-Besides the contract line, the JSON carries
+A plain run does only what the contract line needs: set-up, warm-up, the timed steps, --dump-outputs, the line (plus the
+algorithmic TFLOP/s and GB/s of the step, derived from its time).  With --full the JSON also carries
   roofline     -- the dominant kernel's algorithmic FLOPs / its HIP-event time, measured live in a separate pass
                   (+ the EXECUTED MFMA FLOPs of the same launches: the algebraic folds remove work)
+                  and the encode / decode split of a step (a separate, untimed pass)
+  tolerance_mode, tolerance_mode_mixed -- the fast fp32 model and the fp32 encoder + fp16 decoder on the same workload, timed and
+                  checked against the fixture (N = 1, 16-bit bench dtypes)
   parity       -- latent max / mean |delta| and recon PSNR of THIS build against the reference-generated fixture of the
                   workload (tests/golden/cfg3_sd3_t17_512.npz), in the bench dtype, next to the reference's own noise
-  hbm          -- algorithmic GB/s of the step and the PMC-counted traffic of the committed profile (profiles/)
+  hbm          -- + the PMC-counted traffic of the committed profile (profiles/)
   mfma_busy    -- SQ counter ratio of the dominant kernel from the committed PMC pass (profiles/pmc_sq.json)
-  cpu_baseline -- the CPU oracle (oracle/cvvae_oracle.py, a PyTorch-CPU restatement of the reference: "port") on a
-                  bounded sample of the same workload, on this box's host cores (rank 0, N=1 only).
+  cpu_baseline -- the CPU oracle (oracle/cvvae_oracle.py, a PyTorch-CPU restatement of the reference: "port") on the
+                  workload, on the host's cores (rank 0, N=1 only)
+  reference_ops_on_this_gpu_model -- the kept PyTorch-ROCm figures of the same workload (profiles/r3_torch_gpu_baseline.json)
+The --no-* options below trim a --full run.
 """
 import argparse
 import json
@@ -78,6 +85,10 @@ def parse():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32", "f32q"],
                     help="model dtype; f32 = fp32 model in split precision (three fp16 MFMAs per product), f32q = fp32 model in fast "
                          "split precision (fp16 MFMA + bf8 / fp6 correction MFMA): the cheapest mode inside north_star's 1e-3 latent bound")
+    ap.add_argument("--full", action="store_true",
+                    help="after the line's own steps, also run what it does not need (minutes): encode / decode split, roofline "
+                         "pass, tolerance modes, parity against the fixtures, CPU baseline, kept PyTorch-ROCm figures; N > 1: the "
+                         "sharded == single-process check and the cfg 4 annex.  The --no-* options trim it")
     ap.add_argument("--no-tolerance-mode", action="store_true",
                     help="skip the annex that times and checks the f32q model (the mode that meets |delta| <= 1e-3) beside the bench dtype")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -560,7 +571,7 @@ def main():
     x_full = None
     if tshard:
         # ONE clip, the same on every rank (same seed); the rank keeps only ITS frames on the device
-        x_full, x = temporal_shard_input(T, H, W, world, rank, dtype, "cuda", keep_full=not args.no_check)
+        x_full, x = temporal_shard_input(T, H, W, world, rank, dtype, "cuda", keep_full=args.full and not args.no_check)
     else:
         # cfg 3 / 2: every rank codes its own clip (weak scaling).  cfg 4: every rank holds the same clip (seed without rank)
         g = torch.Generator().manual_seed(1000 + (0 if cfg4 else rank))
@@ -673,7 +684,7 @@ def main():
                 "note": "algorithmic bytes (BASELINE.md section 3) / step time; the path is MFMA-bound (AI ~1900 FLOP/B)"},
     }
 
-    if dist is not None and not args.no_check and (tshard or cfg4):
+    if args.full and dist is not None and not args.no_check and (tshard or cfg4):
         # the sharded run must reproduce the single-process wrapper bit for bit (windows are independent network calls)
         if tshard:
             mom, y_loc = step()
@@ -691,7 +702,7 @@ def main():
         assert out["sharded_equals_single_process"], f"sharded results differ from the single-process run: {[int(v.item()) for v in oks]}"
     x_full = None
 
-    if dist is not None and tshard and not args.no_cfg4_annex:
+    if args.full and dist is not None and tshard and not args.no_cfg4_annex:
         # BASELINE cfg 4 through the same time-sharded step: ONE fixed clip (T = 129, 720x1280: 8 windows x 6 blended spatial
         # tiles), strong scaling, with the single-process time of the same clip measured HERE on rank 0
         fam4, _, T4, H4, W4 = WORKLOADS["cfg4_sd3_T129_720x1280"]
@@ -732,7 +743,7 @@ def main():
         del x4, x4_full
         torch.cuda.empty_cache()
 
-    if rank == 0 and not (tshard or cfg5 or (cfg4 and dist is not None)):
+    if args.full and rank == 0 and not (tshard or cfg5 or (cfg4 and dist is not None)):
         # encode / decode split of one step (separate, untimed pass; events on the launch stream)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         for _ in range(2):
@@ -758,15 +769,15 @@ def main():
                 return vae.decode(vae.encode(x).latent_dist.mode()).sample
         elif cfg4:
             roof_step = None
-    if rank == 0 and not args.no_roofline and roof_step is not None:
+    if args.full and rank == 0 and not args.no_roofline and roof_step is not None:
         vae.enable_hip_graphs(False)  # per-launch timing needs the eager launches
         out.update(roofline_report(roofline_pass(roof_step), args, elapsed / args.steps,
                                    profiled=args.workload.startswith("cfg3") and args.dtype == "bf16"))
         out["hbm"].update(out.pop("hbm_pmc", {}))
     golden = GOLDEN_OF.get("cfg3_sd3_T17_512" if tshard else args.workload)  # (the shard's per-GPU window is cfg 3's clip shape)
     have_golden = golden is not None and os.path.isfile(os.path.join(P.GOLDEN_DIR, golden + ".npz"))
-    tol_mode = (rank == 0 and world == 1 and not args.no_tolerance_mode and not args.no_parity and not args.dtype.startswith("f32")
-                and not cfg5 and have_golden)
+    tol_mode = (args.full and rank == 0 and world == 1 and not args.no_tolerance_mode and not args.no_parity
+                and not args.dtype.startswith("f32") and not cfg5 and have_golden)
     vq = None
     if tol_mode:
         # the SAME workload on the cheapest mode that meets the latent bound as a maximum: throughput, roofline and tolerance of one
@@ -826,12 +837,12 @@ def main():
         vq.decoder_compute_dtype = None
         del xq, zq
     cpu_handle = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_baseline_sample:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_baseline_sample:
         out["cpu_baseline"] = dict(cpu_baseline_measure(family, T, H, W, full=False), measured_in_this_run=True)
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
+    elif args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # every timed region of this run is over: the full-size CPU measurement runs beside the parity legs below
         cpu_handle = cpu_baseline_start(family, T, H, W)
-    if rank == 0 and not args.no_parity and have_golden:
+    if args.full and rank == 0 and not args.no_parity and have_golden:
         vae.enable_hip_graphs(False)
         r = P.measure(vae, golden)
         out["parity"] = {
@@ -843,7 +854,7 @@ def main():
             "north_star_tolerance": "|delta| <= 1e-3 on latents",
             "meets_north_star_tolerance": bool(r["latent_max_abs"] <= 1e-3),
         }
-    if rank == 0 and cfg5 and not args.no_parity and os.path.isfile(os.path.join(P.GOLDEN_DIR, "cfg5slice_sd3_b2_t33_512_enc.npz")):
+    if args.full and rank == 0 and cfg5 and not args.no_parity and os.path.isfile(os.path.join(P.GOLDEN_DIR, "cfg5slice_sd3_b2_t33_512_enc.npz")):
         # cfg 5's own fixture: a B = 2 slice of the batch of 8, both 17-frame windows of every clip, from the reference's modules
         vae.enable_hip_graphs(False)
         r = P.measure_encode(vae, "cfg5slice_sd3_b2_t33_512_enc", latents=lambda xx: vae.encode_latents(xx, sample=False))
@@ -854,7 +865,7 @@ def main():
             "latent_max_abs_per_batch_item": [float(f"{v:.3e}") for v in r["latent_max_abs_per_batch_item"]],
             "north_star_tolerance": "|delta| <= 1e-3 on latents", "meets_north_star_tolerance": bool(r["latent_max_abs"] <= 1e-3),
         }
-    if rank == 0 and cfg4 and not args.no_parity and os.path.isfile(os.path.join(P.GOLDEN_DIR, "cfg4_sd3_t129_720x1280_enc.npz")):
+    if args.full and rank == 0 and cfg4 and not args.no_parity and os.path.isfile(os.path.join(P.GOLDEN_DIR, "cfg4_sd3_t129_720x1280_enc.npz")):
         # cfg 4's own fixture: the WHOLE clip's posterior mean (8 windows x 6 blended tiles) from the reference's modules, encode side
         vae.enable_hip_graphs(False)
         r = P.measure_encode(vae, "cfg4_sd3_t129_720x1280_enc")
@@ -882,7 +893,7 @@ def main():
         del vq
     if cpu_handle is not None:
         out["cpu_baseline"] = cpu_baseline_collect(cpu_handle, args.cpu_baseline_wall, family, T, H, W)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         out["reference_ops_on_this_gpu_model"] = torch_rocm_baseline(family, [B, 3, T, H, W], args.dtype, out["ms_per_step"])
     if dist is not None:
         dist.barrier()

@@ -176,3 +176,14 @@ def test_bench_dump_outputs(tmp_path, monkeypatch):
     monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "0"])
     with pytest.raises(SystemExit):
         bench.parse()
+
+
+def test_bench_full_is_opt_in(monkeypatch):
+    """bench.py: a plain run leaves every extra leg (split, roofline, tolerance modes, parity, CPU baseline, N > 1 check and annex)
+    to --full, whose --no-* options still trim it"""
+    import bench
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--no-cpu-baseline", "--no-parity"])
+    a = bench.parse()
+    assert a.full and a.no_cpu_baseline and a.no_parity and not a.no_roofline

@@ -11,7 +11,7 @@ O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 # 1 warm-up + 3 timed steps + the 2 passes of the encode/decode split = 6 steps per run
-BENCH=${PROFILE_CMD:-"python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-parity $*"}
+BENCH=${PROFILE_CMD:-"python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-parity $*"}
 STEPS=${PROFILE_STEPS:-6}
 rocprofv3 --kernel-trace --stats -d $O/trace -o bench -- $BENCH > $O/trace.log 2>&1
 DB=$(find $O/trace -name "*.db" | head -1)
