@@ -12,7 +12,7 @@ F16, BF16, F32, F32Q, F32Q6 = 0, 1, 2, 3, 4
 PAD_ZERO, PAD_REPLICATE = 0, 1
 PRO_NONE, PRO_GN_SILU, PRO_GN = 0, 1, 2
 OUT_NDHWC, OUT_NCDHW, OUT_TIME_SHUFFLE = 0, 1, 2
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class ConvDesc(ctypes.Structure):
@@ -94,6 +94,14 @@ PROTOTYPES = {
     "cvvae_frames_u8_to_ndhwc": (_i32, [_i32, _vp, _i64, _i32, _vp, _vp]),
     "cvvae_ncdhw_to_frames_u8": (_i32, [_i32, _vp, _i64, _vp, _vp]),
     "cvvae_blend": (_i32, [_i32, _vp, _i32, _i32, _vp, _i32, _i32, _i64, _i32, _i32, _vp]),
+    "cvvae_lpips_scale_in": (_i32, [_i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "cvvae_lpips_scale_in_bwd": (_i32, [_i32, _i32, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp]),
+    "cvvae_relu": (_i32, [_i32, _vp, _i64, _vp, _vp]),
+    "cvvae_maxpool2x2": (_i32, [_i32, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "cvvae_relu_pool_bwd": (_i32, [_i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "cvvae_lpips_head_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i32]),
+    "cvvae_lpips_head": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "cvvae_lpips_head_bwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -907,3 +907,105 @@ def ncdhw_to_frames_u8(x: torch.Tensor) -> torch.Tensor:
     L.check(lib.cvvae_ncdhw_to_frames_u8(_dt(x.dtype), x.data_ptr(), T * H * W, out.data_ptr(), _stream(x)),
             "cvvae_ncdhw_to_frames_u8")
     return out
+
+
+# ---- the passes around the VGG16 convolutions of the LPIPS perceptual loss (include/cvvae.h ABI 14; cvvae_amd/lpips.py) ----
+def lpips_scale_in(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, cpad: int, dtype: torch.dtype,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x: [N,3,H,W] (fp16 / bf16 / fp32) -> NHWC [N,H,W,cpad] `dtype` = (x - shift[c]) / scale[c], pad channels zero (ScalingLayer +
+    layout).  shift / scale: fp32 [3].  out: a contiguous [N,H,W,cpad] tensor (or slice of one) to write into."""
+    lib = L.load()
+    _need_gpu(x)
+    x = x.contiguous()
+    N, C, H, W = x.shape
+    assert C == 3 and shift.dtype == torch.float32 and scale.dtype == torch.float32 and shift.numel() == 3 and scale.numel() == 3
+    if out is None:
+        out = torch.empty((N, H, W, cpad), dtype=dtype, device=x.device)
+    assert tuple(out.shape) == (N, H, W, cpad) and out.dtype == dtype and out.is_contiguous()
+    L.check(lib.cvvae_lpips_scale_in(_dt(x.dtype), _dt(dtype), x.data_ptr(), N, H, W, shift.data_ptr(), scale.data_ptr(), cpad,
+                                     out.data_ptr(), _stream(x)), "cvvae_lpips_scale_in")
+    return out
+
+
+def lpips_scale_in_bwd(g: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """g: NHWC [N,H,W,Cs] gradient -> [N,3,H,W] `dtype` = g[..., c] / scale[c] of the first 3 channels (the adjoint of lpips_scale_in)"""
+    lib = L.load()
+    _need_gpu(g)
+    assert g.dim() == 4 and g.is_contiguous() and scale.dtype == torch.float32 and scale.numel() == 3
+    N, H, W, Cs = g.shape
+    out = torch.empty((N, 3, H, W), dtype=dtype, device=g.device)
+    L.check(lib.cvvae_lpips_scale_in_bwd(_dt(g.dtype), _dt(dtype), g.data_ptr(), N, H, W, Cs, scale.data_ptr(), out.data_ptr(),
+                                         _stream(g)), "cvvae_lpips_scale_in_bwd")
+    return out
+
+
+def relu_(x: torch.Tensor) -> torch.Tensor:
+    """max(x, 0) in place (cvvae_relu)"""
+    lib = L.load()
+    _need_gpu(x)
+    assert x.is_contiguous()
+    L.check(lib.cvvae_relu(_dt(x.dtype), x.data_ptr(), x.numel(), x.data_ptr(), _stream(x)), "cvvae_relu")
+    return x
+
+
+def maxpool2x2(x: torch.Tensor) -> torch.Tensor:
+    """x: [..., H, W, C] -> [..., H//2, W//2, C]: nn.MaxPool2d(2, 2) on channels-last frames"""
+    lib = L.load()
+    _need_gpu(x)
+    assert x.dim() >= 3 and x.is_contiguous()
+    H, W, C = x.shape[-3:]
+    N = x.numel() // (H * W * C)
+    out = torch.empty((*x.shape[:-3], H // 2, W // 2, C), dtype=x.dtype, device=x.device)
+    L.check(lib.cvvae_maxpool2x2(_dt(x.dtype), x.data_ptr(), N, H, W, C, out.data_ptr(), _stream(x)), "cvvae_maxpool2x2")
+    return out
+
+
+def relu_pool_bwd(y: torch.Tensor, g_tap: Optional[torch.Tensor], g_pool: Optional[torch.Tensor]) -> torch.Tensor:
+    """(g_tap + unpool(g_pool)) * (y > 0) for a ReLU output y [..., H, W, C] that was tapped and / or 2x2-max-pooled: g_tap shaped as
+    y, g_pool [..., H//2, W//2, C]; either may be None.  Ties go to the first maximum in row-major order, as ATen's."""
+    lib = L.load()
+    _need_gpu(y)
+    assert y.dim() >= 3 and y.is_contiguous()
+    H, W, C = y.shape[-3:]
+    N = y.numel() // (H * W * C)
+    if g_tap is not None:
+        assert g_tap.shape == y.shape and g_tap.dtype == y.dtype and g_tap.is_contiguous()
+    if g_pool is not None:
+        assert tuple(g_pool.shape) == (*y.shape[:-3], H // 2, W // 2, C) and g_pool.dtype == y.dtype and g_pool.is_contiguous()
+    out = torch.empty_like(y)
+    L.check(lib.cvvae_relu_pool_bwd(_dt(y.dtype), y.data_ptr(), g_tap.data_ptr() if g_tap is not None else None,
+                                    g_pool.data_ptr() if g_pool is not None else None, N, H, W, C, out.data_ptr(), _stream(y)),
+            "cvvae_relu_pool_bwd")
+    return out
+
+
+def lpips_head(f0: torch.Tensor, f1: torch.Tensor, w: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out[n] += mean over pixels of sum_c w_c (f0_c / m0 - f1_c / m1)^2, m = sqrt(sum f^2 + 1e-10) + 1e-10: one LPIPS level.
+    f0, f1: [N, ..., C] features (same shape), w: fp32 [C], out: fp32 [N] (zeroed by the caller before the first level)."""
+    lib = L.load()
+    _need_gpu(f0)
+    assert f0.shape == f1.shape and f0.dtype == f1.dtype and f0.is_contiguous() and f1.is_contiguous()
+    N, C = f0.shape[0], f0.shape[-1]
+    HW = f0.numel() // (N * C)
+    assert w.dtype == torch.float32 and w.numel() == C and w.is_contiguous() and out.dtype == torch.float32 and out.numel() == N
+    ws = torch.empty(max(int(lib.cvvae_lpips_head_workspace_bytes(N, HW, C)), 16), dtype=torch.uint8, device=f0.device)
+    L.check(lib.cvvae_lpips_head(_dt(f0.dtype), f0.data_ptr(), f1.data_ptr(), w.data_ptr(), N, HW, C, out.data_ptr(), ws.data_ptr(),
+                                 _stream(f0)), "cvvae_lpips_head")
+    return out
+
+
+def lpips_head_bwd(f0: torch.Tensor, f1: torch.Tensor, w: torch.Tensor, gout: torch.Tensor, g0: Optional[torch.Tensor],
+                   g1: Optional[torch.Tensor]) -> None:
+    """writes dL/df0 into g0 and / or dL/df1 into g1 (shaped and typed as the features; None skips that side) given gout fp32 [N]"""
+    lib = L.load()
+    _need_gpu(f0)
+    assert f0.shape == f1.shape and f0.dtype == f1.dtype and f0.is_contiguous() and f1.is_contiguous()
+    N, C = f0.shape[0], f0.shape[-1]
+    HW = f0.numel() // (N * C)
+    assert w.dtype == torch.float32 and w.numel() == C and w.is_contiguous()
+    assert gout.dtype == torch.float32 and gout.numel() == N and gout.is_contiguous()
+    for g in (g0, g1):
+        assert g is None or (g.shape == f0.shape and g.dtype == f0.dtype and g.is_contiguous())
+    L.check(lib.cvvae_lpips_head_bwd(_dt(f0.dtype), f0.data_ptr(), f1.data_ptr(), w.data_ptr(), gout.data_ptr(), N, HW, C,
+                                     g0.data_ptr() if g0 is not None else None, g1.data_ptr() if g1 is not None else None,
+                                     _stream(f0)), "cvvae_lpips_head_bwd")

@@ -23,7 +23,9 @@
 extern "C" {
 #endif
 
-#define CVVAE_ABI_VERSION 13
+/* ABI 14: the LPIPS perceptual-loss passes (cvvae_lpips_scale_in / _bwd, cvvae_relu, cvvae_maxpool2x2, cvvae_relu_pool_bwd,
+ * cvvae_lpips_head / _bwd); no existing entry point or struct changed. */
+#define CVVAE_ABI_VERSION 14
 
 /* cvvae dtype.  CVVAE_F32 = the reference's fp32 model path (from_pretrained without torch_dtype, models/modeling_vae.py:41-42
  * force_upcast): activations, residuals, outputs and the source weights are float; the kernels split every fp32 operand into
@@ -428,6 +430,50 @@ int cvvae_ncdhw_to_frames_u8(int32_t dtype, const void* in, int64_t thw, uint8_t
  * rows = B*C*T.  a is [rows][Ha][Wa], b is [rows][Hb][Wb]. */
 int cvvae_blend(int32_t dtype, const void* a, int32_t Ha, int32_t Wa, void* b, int32_t Hb, int32_t Wb, int64_t rows,
                 int32_t overlap, int32_t axis, void* stream);
+
+/*
+ * The LPIPS perceptual term of the training loss (ABI 14; cvvae_amd/lpips.py): `p_loss = self.perceptual_loss(inputs, reconstructions)`
+ * of lvdm/modules/autoencoding/losses/discriminator_loss.py:252-256, 459-463 is LPIPS().eval() -- a frozen VGG16 trunk
+ * (lvdm/modules/autoencoding/lpips/loss/lpips.py:99-138) whose thirteen 3x3 convolutions run on cvvae_conv_fwd's (1,3,3) family, forward
+ * and input gradient.  The entries below are the passes around them (csrc/lpips_kernels.hip): NHWC tensors [N][H][W][C] of `dtype`
+ * (CVVAE_F16 / CVVAE_BF16 / CVVAE_F32), C % 8 == 0, fp32 arithmetic with one rounding to the storage dtype, one read and one write
+ * per tensor, no atomics.
+ *
+ * cvvae_lpips_scale_in: ScalingLayer (lpips.py:67-78) + layout: in [N][3][H][W] of src_dtype -> out [N][H][W][Cpad] of dst_dtype,
+ * channel c < 3 = (x - shift[c]) / scale[c] (shift, scale: fp32 [3], device), channels 3 .. Cpad-1 zero (Cpad = the first conv's K-chunk).
+ * cvvae_lpips_scale_in_bwd: its adjoint: g [N][H][W] with pix_stride elements per pixel (g_dtype) -> out [N][3][H][W] (dst_dtype) =
+ * g[c] / scale[c] of the first 3 channels.
+ */
+int cvvae_lpips_scale_in(int32_t src_dtype, int32_t dst_dtype, const void* in, int64_t N, int32_t H, int32_t W, const float* shift,
+                         const float* scale, int32_t Cpad, void* out, void* stream);
+int cvvae_lpips_scale_in_bwd(int32_t g_dtype, int32_t dst_dtype, const void* g, int64_t N, int32_t H, int32_t W, int64_t pix_stride,
+                             const float* scale, void* out, void* stream);
+/* aten::relu over n elements (n % 8 == 0); out == x (in place) is allowed. */
+int cvvae_relu(int32_t dtype, const void* x, int64_t n, void* out, void* stream);
+/* nn.MaxPool2d(2, 2) (torchvision VGG16 features 4, 9, 16, 23): x [N][H][W][C] -> out [N][H/2][W/2][C], odd extents floored. */
+int cvvae_maxpool2x2(int32_t dtype, const void* x, int64_t N, int32_t H, int32_t W, int32_t C, void* out, void* stream);
+/*
+ * Backward of "ReLU output y, tapped by a head, then max-pooled" in one pass (aten::threshold_backward + aten::max_pool2d_with_indices_backward
+ * + the add of the two branches):  gx = (g_tap + unpool(g_pool)) * (y > 0).  y, g_tap, gx: [N][H][W][C]; g_pool: [N][H/2][W/2][C].  The
+ * pooled gradient goes to the FIRST maximum of each 2x2 window in row-major scan order (ATen's tie rule), recomputed from y (no index
+ * tensor).  g_tap or g_pool may be NULL (not both): an interior ReLU passes its successor's gradient as g_tap and no g_pool.
+ */
+int cvvae_relu_pool_bwd(int32_t dtype, const void* y, const void* g_tap, const void* g_pool, int64_t N, int32_t H, int32_t W,
+                        int32_t C, void* gx, void* stream);
+/*
+ * One level of LPIPS.forward (lpips.py:46-64): f0, f1 [N][HW][C] features, w fp32 [C] (the level's 1x1 lin weight).  Per pixel
+ * m = sqrt(sum_c f_c^2 + 1e-10) + 1e-10 (normalize_tensor, both eps), d = sum_c w_c (f0_c / m0 - f1_c / m1)^2;
+ * out[n] += mean over the HW pixels of d -- `out` is fp32 [N], zeroed by the caller before the first level.  Two launches: per-workgroup
+ * partial sums into `workspace` (cvvae_lpips_head_workspace_bytes), merged in index order: bit-reproducible.  C in {64, 128, 256, 512}
+ * (a pixel's channels sit in one wave; else CVVAE_EUNSUPPORTED).
+ * cvvae_lpips_head_bwd: given gout fp32 [N] = dL/d out, writes g_f0 and / or g_f1 (`dtype`, shaped as the features; a NULL pointer
+ * skips that side) in one pass that recomputes m, e and the per-pixel dots sum_c w_c e_c f_c.
+ */
+size_t cvvae_lpips_head_workspace_bytes(int64_t N, int64_t HW, int32_t C);
+int cvvae_lpips_head(int32_t dtype, const void* f0, const void* f1, const float* w, int64_t N, int64_t HW, int32_t C, float* out,
+                     void* workspace, void* stream);
+int cvvae_lpips_head_bwd(int32_t dtype, const void* f0, const void* f1, const float* w, const float* gout, int64_t N, int64_t HW,
+                         int32_t C, void* g_f0, void* g_f1, void* stream);
 
 int cvvae_abi_version(void);
 /* name of the kernel instance cvvae_conv_fwd would launch for d (for profiling reports); NULL if unsupported */
