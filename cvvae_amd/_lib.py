@@ -13,6 +13,8 @@ PAD_ZERO, PAD_REPLICATE = 0, 1
 PRO_NONE, PRO_GN_SILU, PRO_GN = 0, 1, 2
 OUT_NDHWC, OUT_NCDHW, OUT_TIME_SHUFFLE = 0, 1, 2
 ABI_VERSION = 14
+# cvvae_reduce_sum's f_op (include/cvvae.h CVVAE_RED_*)
+RED_ABS_DIFF, RED_SQ_DIFF, RED_SQ, RED_IDENT, RED_HINGE_NEG, RED_HINGE_POS, RED_SOFTPLUS_NEG, RED_SOFTPLUS_POS = range(8)
 
 
 class ConvDesc(ctypes.Structure):
@@ -42,6 +44,12 @@ class ConvDesc(ctypes.Structure):
         ("four_wave", ctypes.c_int32),
         ("act_bound_dev", ctypes.c_void_p),
     ]
+
+
+class ReduceShape(ctypes.Structure):
+    """mirror of `cvvae_reduce_shape` (include/cvvae.h)"""
+
+    _fields_ = [("n", ctypes.c_int64 * 3), ("L", ctypes.c_int64), ("sa", ctypes.c_int64 * 3), ("sb", ctypes.c_int64 * 3)]
 
 
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
@@ -102,6 +110,11 @@ PROTOTYPES = {
     "cvvae_lpips_head_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i32]),
     "cvvae_lpips_head": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
     "cvvae_lpips_head_bwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "cvvae_reduce_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(ReduceShape)]),
+    "cvvae_reduce_sum": (_i32, [_i32, _i32, _vp, _i32, _vp, ctypes.POINTER(ReduceShape), _vp, _vp, _vp]),
+    "cvvae_reduce_sum_bwd": (_i32, [_i32, _i32, _vp, _i32, _vp, ctypes.POINTER(ReduceShape), _vp, _vp, _vp, _vp]),
+    "cvvae_gauss_reg": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "cvvae_gauss_reg_bwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
 }
 
 _lib = None
@@ -109,7 +122,7 @@ _lib = None
 
 # translation units whose kernels only run in training (weight gradients, channel sums, their reductions): no launch of an
 # encode / decode step comes from them, so the counters of the inference bench do not go stale when they change
-TRAINING_ONLY_SOURCES = ("wgrad_kernel.hip",)
+TRAINING_ONLY_SOURCES = ("wgrad_kernel.hip", "loss_kernels.hip")
 
 
 def source_fingerprint() -> str:

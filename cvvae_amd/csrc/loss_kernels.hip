@@ -1,0 +1,442 @@
+// loss_kernels.hip -- the passes of the training loss around the networks (cvvae_amd/loss.py): a deterministic map-reduce to one
+// fp32 scalar (pixel terms, KL, the GAN terms, the gradient norms of the adaptive weight), its adjoint, and the diagonal-Gaussian
+// posterior (sample + KL) forward and backward.  gfx950 only.  All of them are HBM- or latency-bound: plain C++.
+//
+// Order of summation.  Elements are numbered by their LOGICAL index i (outer dimensions slowest, the inner run fastest).  Group
+// g = elements [8g, 8g + 8) belongs to thread g % 256 of tile g / 256; workgroup w walks tiles w, w + grid, ...; a thread adds
+// its groups serially (each group's 8 terms first, in index order), the 64 lanes of a wave are merged by a butterfly, the four
+// waves through LDS in wave order, and stage 2 (one workgroup) merges the per-workgroup partials the same way.  The grid is a
+// function of the element count alone and nothing is atomic, so the sum is a function of the logical values alone: the same
+// inputs give the same bits on every run, and so do a strided view and its contiguous copy, at any alignment.
+// A group is read with 16-byte loads when it lies inside one inner run and its address is 16-byte aligned, element by element
+// otherwise (the head and tail of a run whose length or base is not a multiple of 8 elements).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/cvvae.h"
+
+namespace cvvae {
+namespace loss {
+
+constexpr int WG = 256;              // threads per workgroup
+constexpr int VEC = 8;               // elements per group
+constexpr int TILE = WG * VEC;       // elements per workgroup pass
+constexpr int MAX_BLOCKS = 2048;     // stage-1 grid cap = stage-2's serial depth x 256
+
+template <typename T>
+__device__ __forceinline__ bool aligned16(const T* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+template <typename T>
+__device__ __forceinline__ void load8(const T* p, float (&f)[VEC]);
+template <>
+__device__ __forceinline__ void load8<float>(const float* p, float (&f)[VEC]) {
+  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
+  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
+}
+template <typename T>
+__device__ __forceinline__ void load8_16bit(const T* p, float (&f)[VEC]) {
+  union { uint4 u; T h[VEC]; } v;
+  v.u = *reinterpret_cast<const uint4*>(p);
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) f[j] = (float)v.h[j];
+}
+template <>
+__device__ __forceinline__ void load8<_Float16>(const _Float16* p, float (&f)[VEC]) { load8_16bit<_Float16>(p, f); }
+template <>
+__device__ __forceinline__ void load8<__bf16>(const __bf16* p, float (&f)[VEC]) { load8_16bit<__bf16>(p, f); }
+
+// 8 values rounded once (nearest even) to T, stored as 16-byte vectors when p allows it
+template <typename T>
+__device__ __forceinline__ void store8(T* p, const float (&f)[VEC], int n) {
+  if (n == VEC && aligned16(p)) {
+    if constexpr (sizeof(T) == 4) {
+      reinterpret_cast<float4*>(p)[0] = make_float4(f[0], f[1], f[2], f[3]);
+      reinterpret_cast<float4*>(p)[1] = make_float4(f[4], f[5], f[6], f[7]);
+    } else {
+      union { uint4 u; T h[VEC]; } v;
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) v.h[j] = (T)f[j];
+      *reinterpret_cast<uint4*>(p) = v.u;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < VEC; ++j)
+      if (j < n) p[j] = (T)f[j];
+  }
+}
+
+// up to three outer dimensions (slowest first) with one operand's element strides, and the inner run
+struct View {
+  long long n1, n2, L, s0, s1, s2;
+  __device__ __forceinline__ long long offset(long long row, long long j) const {
+    const long long i2 = row % n2, r = row / n2;
+    return (r / n1) * s0 + (r % n1) * s1 + i2 * s2 + j;
+  }
+};
+
+// the n (<= 8) elements of logical indices [i, i + n) of a strided operand
+template <typename T>
+__device__ __forceinline__ void gather8(const T* p, const View& v, long long i, int n, float (&f)[VEC]) {
+  const long long row = i / v.L, j = i - row * v.L;
+  if (n == VEC && j + VEC <= v.L) {
+    const T* q = p + v.offset(row, j);
+    if (aligned16(q)) {
+      load8<T>(q, f);
+    } else {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) f[k] = (float)q[k];
+    }
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) {
+    f[k] = 0.f;
+    if (k < n) {
+      const long long r = (i + k) / v.L;
+      f[k] = (float)p[v.offset(r, (i + k) - r * v.L)];
+    }
+  }
+}
+
+// aten::softplus (beta 1, threshold 20) and its derivative
+__device__ __forceinline__ float softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }
+__device__ __forceinline__ float softplus_grad(float x) {
+  if (x > 20.f) return 1.f;
+  const float z = expf(x);
+  return z / (z + 1.f);
+}
+
+__device__ __forceinline__ float term(int op, float a, float b) {
+  switch (op) {
+    case CVVAE_RED_ABS_DIFF: return fabsf(a - b);
+    case CVVAE_RED_SQ_DIFF: { const float d = a - b; return d * d; }
+    case CVVAE_RED_SQ: return a * a;
+    case CVVAE_RED_IDENT: return a;
+    case CVVAE_RED_HINGE_NEG: return fmaxf(1.f - a, 0.f);
+    case CVVAE_RED_HINGE_POS: return fmaxf(1.f + a, 0.f);
+    case CVVAE_RED_SOFTPLUS_NEG: return softplus(-a);
+    default: return softplus(a);
+  }
+}
+
+// d f_op / d a (two-operand ops: d / d b is its negative).  sign(0) = 0; the hinges' sub-gradient is relu's strict inequality
+__device__ __forceinline__ float term_grad(int op, float a, float b) {
+  switch (op) {
+    case CVVAE_RED_ABS_DIFF: { const float d = a - b; return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
+    case CVVAE_RED_SQ_DIFF: return 2.f * (a - b);
+    case CVVAE_RED_SQ: return 2.f * a;
+    case CVVAE_RED_IDENT: return 1.f;
+    case CVVAE_RED_HINGE_NEG: return (1.f - a) > 0.f ? -1.f : 0.f;
+    case CVVAE_RED_HINGE_POS: return (1.f + a) > 0.f ? 1.f : 0.f;
+    case CVVAE_RED_SOFTPLUS_NEG: return -softplus_grad(-a);
+    default: return softplus_grad(a);
+  }
+}
+
+// workgroup sum in a fixed order, valid in thread 0
+__device__ __forceinline__ float block_sum(float x) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) x += __shfl_xor(x, m, 64);
+  __shared__ float sh[WG / 64];
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
+  __syncthreads();
+  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+template <typename TA, typename TB>
+__global__ __launch_bounds__(WG) void reduce_partial_kernel(int op, const TA* __restrict__ a, View va, const TB* __restrict__ b,
+                                                            View vb, long long total, float* __restrict__ ws) {
+  const long long ntiles = (total + TILE - 1) / TILE;
+  float acc = 0.f;
+  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const long long i = (t * WG + threadIdx.x) * VEC;
+    if (i >= total) continue;
+    const int n = (total - i) < VEC ? (int)(total - i) : VEC;
+    float fa[VEC], fb[VEC];
+    gather8<TA>(a, va, i, n, fa);
+    if (b) {
+      gather8<TB>(b, vb, i, n, fb);
+    } else {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) fb[k] = 0.f;
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) s += (k < n) ? term(op, fa[k], fb[k]) : 0.f;
+    acc += s;
+  }
+  acc = block_sum(acc);
+  if (threadIdx.x == 0) ws[blockIdx.x] = acc;
+}
+
+// stage 2: out = scale * (the nblk partials, thread t taking t, t + 256, ... serially, then the workgroup sum)
+__global__ __launch_bounds__(WG) void reduce_final_kernel(const float* __restrict__ ws, int nblk, float scale, float* __restrict__ out) {
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < nblk; i += WG) acc += ws[i];
+  acc = block_sum(acc);
+  if (threadIdx.x == 0) out[0] = scale * acc;
+}
+
+template <typename TA, typename TB>
+__global__ __launch_bounds__(WG) void reduce_bwd_kernel(int op, const TA* __restrict__ a, View va, const TB* __restrict__ b, View vb,
+                                                        long long total, const float* __restrict__ coef_dev, TA* __restrict__ ga,
+                                                        TB* __restrict__ gb) {
+  const float coef = coef_dev[0];
+  const long long ntiles = (total + TILE - 1) / TILE;
+  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const long long i = (t * WG + threadIdx.x) * VEC;
+    if (i >= total) continue;
+    const int n = (total - i) < VEC ? (int)(total - i) : VEC;
+    float fa[VEC], fb[VEC], g[VEC];
+    gather8<TA>(a, va, i, n, fa);
+    if (b) {
+      gather8<TB>(b, vb, i, n, fb);
+    } else {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) fb[k] = 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) g[k] = coef * term_grad(op, fa[k], fb[k]);
+    if (ga) store8<TA>(ga + i, g, n);
+    if (gb) {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) g[k] = -g[k];
+      store8<TB>(gb + i, g, n);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// DiagonalGaussianDistribution (lvdm/modules/distributions/distributions.py:24-52) in one pass: moments [B][2C][S] chunked at
+// channel C into mean and logvar, logvar clamped to [-30, 20], z = mean + exp(0.5 logvar) * noise (noise NULL: z = mean), and the
+// partial sums of mean^2 + var - 1 - logvar.  Rows are the B samples, the inner run the C * S values of one chunk.
+// ---------------------------------------------------------------------------------------------------------
+constexpr float LOGVAR_MIN = -30.f, LOGVAR_MAX = 20.f;
+
+template <typename T>
+__global__ __launch_bounds__(WG) void gauss_reg_kernel(const T* __restrict__ mom, const T* __restrict__ noise, T* __restrict__ z,
+                                                       long long CS, long long total, float* __restrict__ ws) {
+  const View vm{1, 1 << 30, CS, 0, 0, 2 * CS};  // row b of the mean chunk starts at b * 2CS (n2 only has to exceed B)
+  const long long ntiles = (total + TILE - 1) / TILE;
+  float acc = 0.f;
+  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const long long i = (t * WG + threadIdx.x) * VEC;
+    if (i >= total) continue;
+    const int n = (total - i) < VEC ? (int)(total - i) : VEC;
+    float m[VEC], lv[VEC], e[VEC], o[VEC];
+    gather8<T>(mom, vm, i, n, m);
+    gather8<T>(mom + CS, vm, i, n, lv);
+    if (noise) {
+      if (n == VEC && aligned16(noise + i)) {
+        load8<T>(noise + i, e);
+      } else {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) e[k] = (k < n) ? (float)noise[i + k] : 0.f;
+      }
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      const float l = fminf(fmaxf(lv[k], LOGVAR_MIN), LOGVAR_MAX);
+      o[k] = noise ? __builtin_fmaf(expf(0.5f * l), e[k], m[k]) : m[k];
+      s += (k < n) ? (m[k] * m[k] + expf(l) - 1.f - l) : 0.f;
+    }
+    store8<T>(z + i, o, n);
+    acc += s;
+  }
+  acc = block_sum(acc);
+  if (threadIdx.x == 0) ws[blockIdx.x] = acc;
+}
+
+// adjoint:  d mean = g_z + coef mean;  d logvar = (g_z noise 0.5 std + coef 0.5 (var - 1)) [-30 <= logvar_raw <= 20]
+template <typename T>
+__global__ __launch_bounds__(WG) void gauss_reg_bwd_kernel(const T* __restrict__ mom, const T* __restrict__ noise,
+                                                           const T* __restrict__ gz, const float* __restrict__ coef_dev,
+                                                           T* __restrict__ gmom, long long CS, long long total) {
+  const float coef = coef_dev[0];
+  const View vm{1, 1 << 30, CS, 0, 0, 2 * CS};
+  const long long ntiles = (total + TILE - 1) / TILE;
+  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const long long i = (t * WG + threadIdx.x) * VEC;
+    if (i >= total) continue;
+    const int n = (total - i) < VEC ? (int)(total - i) : VEC;
+    float m[VEC], lv[VEC], e[VEC], g[VEC], dm[VEC], dl[VEC];
+    gather8<T>(mom, vm, i, n, m);
+    gather8<T>(mom + CS, vm, i, n, lv);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) e[k] = g[k] = 0.f;
+    if (gz) {
+      if (n == VEC && aligned16(gz + i)) {
+        load8<T>(gz + i, g);
+      } else {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) g[k] = (k < n) ? (float)gz[i + k] : 0.f;
+      }
+      if (noise) {
+        if (n == VEC && aligned16(noise + i)) {
+          load8<T>(noise + i, e);
+        } else {
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) e[k] = (k < n) ? (float)noise[i + k] : 0.f;
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      const bool in = lv[k] >= LOGVAR_MIN && lv[k] <= LOGVAR_MAX;
+      const float l = fminf(fmaxf(lv[k], LOGVAR_MIN), LOGVAR_MAX);
+      dm[k] = __builtin_fmaf(coef, m[k], g[k]);
+      dl[k] = in ? (g[k] * e[k] * 0.5f * expf(0.5f * l) + coef * 0.5f * (expf(l) - 1.f)) : 0.f;
+    }
+    // element i = (b, r) of a chunk lands at b * 2CS + r (mean) and b * 2CS + CS + r (logvar)
+    const long long row = i / CS, r = i - row * CS;
+    if (n == VEC && r + VEC <= CS) {
+      store8<T>(gmom + row * 2 * CS + r, dm, VEC);
+      store8<T>(gmom + row * 2 * CS + CS + r, dl, VEC);
+    } else {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        if (k >= n) continue;
+        const long long rw = (i + k) / CS, rr = (i + k) - rw * CS;
+        gmom[rw * 2 * CS + rr] = (T)dm[k];
+        gmom[rw * 2 * CS + CS + rr] = (T)dl[k];
+      }
+    }
+  }
+}
+
+static inline long long blocks_for(long long total) {
+  const long long tiles = (total + TILE - 1) / TILE;
+  return tiles < MAX_BLOCKS ? tiles : MAX_BLOCKS;
+}
+
+// element count of a shape, or <= 0 when it is malformed / beyond what the index arithmetic holds
+static inline long long shape_total(const cvvae_reduce_shape* s, bool two) {
+  if (!s) return 0;
+  long long total = 1;
+  for (int d = 0; d < 3; ++d) {
+    if (s->n[d] <= 0 || s->sa[d] < 0 || (two && s->sb[d] < 0)) return 0;
+    if (s->n[d] > (1LL << 40) / total) return -1;
+    total *= s->n[d];
+  }
+  if (s->L <= 0) return 0;
+  if (s->L > (1LL << 40) / total) return -1;
+  return total * s->L;
+}
+
+static inline bool known_dtype(int32_t d) { return d == CVVAE_F16 || d == CVVAE_BF16 || d == CVVAE_F32; }
+static inline bool known_op(int32_t op) { return op >= CVVAE_RED_ABS_DIFF && op <= CVVAE_RED_SOFTPLUS_POS; }
+static inline bool two_operands(int32_t op) { return op == CVVAE_RED_ABS_DIFF || op == CVVAE_RED_SQ_DIFF; }
+
+}  // namespace loss
+}  // namespace cvvae
+
+using namespace cvvae::loss;
+
+#define CHECK_LAUNCH() return (int)hipGetLastError()
+
+// CALL(TA, TB) for the pair (dtype_a, dtype_b); both are known dtypes by the time this runs
+#define LOSS_BY_PAIR(CALL) \
+  do { \
+    if (dtype_a == CVVAE_F32) { \
+      if (dtype_b == CVVAE_F32) { CALL(float, float); } else if (dtype_b == CVVAE_F16) { CALL(float, _Float16); } else { CALL(float, __bf16); } \
+    } else if (dtype_a == CVVAE_F16) { \
+      if (dtype_b == CVVAE_F32) { CALL(_Float16, float); } else if (dtype_b == CVVAE_F16) { CALL(_Float16, _Float16); } else { CALL(_Float16, __bf16); } \
+    } else { \
+      if (dtype_b == CVVAE_F32) { CALL(__bf16, float); } else if (dtype_b == CVVAE_F16) { CALL(__bf16, _Float16); } else { CALL(__bf16, __bf16); } \
+    } \
+  } while (0)
+
+#define LOSS_BY_DTYPE(CALL) \
+  do { \
+    if (dtype == CVVAE_F32) { CALL(float); } else if (dtype == CVVAE_F16) { CALL(_Float16); } else { CALL(__bf16); } \
+  } while (0)
+
+extern "C" {
+
+size_t cvvae_reduce_workspace_bytes(const cvvae_reduce_shape* shape) {
+  const long long total = shape_total(shape, false);
+  if (total <= 0) return 0;
+  return (size_t)blocks_for(total) * sizeof(float);
+}
+
+int cvvae_reduce_sum(int32_t op, int32_t dtype_a, const void* a, int32_t dtype_b, const void* b, const cvvae_reduce_shape* shape,
+                     void* workspace, float* out, void* stream) {
+  if (!a || !shape || !workspace || !out) return CVVAE_EINVAL;
+  if (!known_op(op) || !known_dtype(dtype_a) || (b && !known_dtype(dtype_b))) return CVVAE_EUNSUPPORTED;
+  const bool two = two_operands(op);
+  if (two != (b != nullptr)) return CVVAE_EINVAL;
+  const long long total = shape_total(shape, two);
+  if (total == 0) return CVVAE_EINVAL;
+  if (total < 0) return CVVAE_EUNSUPPORTED;
+  if (!b) dtype_b = CVVAE_F32;
+  const View va{shape->n[1], shape->n[2], shape->L, shape->sa[0], shape->sa[1], shape->sa[2]};
+  const View vb{shape->n[1], shape->n[2], shape->L, shape->sb[0], shape->sb[1], shape->sb[2]};
+  const int nblk = (int)blocks_for(total);
+  hipStream_t s = (hipStream_t)stream;
+#define CALL(TA, TB) \
+  hipLaunchKernelGGL((reduce_partial_kernel<TA, TB>), dim3(nblk), dim3(WG), 0, s, op, (const TA*)a, va, (const TB*)b, vb, total, \
+                     (float*)workspace)
+  LOSS_BY_PAIR(CALL);
+#undef CALL
+  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(WG), 0, s, (const float*)workspace, nblk, 1.0f, out);
+  CHECK_LAUNCH();
+}
+
+int cvvae_reduce_sum_bwd(int32_t op, int32_t dtype_a, const void* a, int32_t dtype_b, const void* b, const cvvae_reduce_shape* shape,
+                         const float* coef_dev, void* ga, void* gb, void* stream) {
+  if (!a || !shape || !coef_dev || (!ga && !gb)) return CVVAE_EINVAL;
+  if (!known_op(op) || !known_dtype(dtype_a) || (b && !known_dtype(dtype_b))) return CVVAE_EUNSUPPORTED;
+  const bool two = two_operands(op);
+  if (two != (b != nullptr) || (gb && !two)) return CVVAE_EINVAL;
+  const long long total = shape_total(shape, two);
+  if (total == 0) return CVVAE_EINVAL;
+  if (total < 0) return CVVAE_EUNSUPPORTED;
+  if (!b) dtype_b = CVVAE_F32;
+  const View va{shape->n[1], shape->n[2], shape->L, shape->sa[0], shape->sa[1], shape->sa[2]};
+  const View vb{shape->n[1], shape->n[2], shape->L, shape->sb[0], shape->sb[1], shape->sb[2]};
+  const long long tiles = (total + TILE - 1) / TILE;
+  const int nblk = (int)(tiles < 65536 ? tiles : 65536);
+  hipStream_t s = (hipStream_t)stream;
+#define CALL(TA, TB) \
+  hipLaunchKernelGGL((reduce_bwd_kernel<TA, TB>), dim3(nblk), dim3(WG), 0, s, op, (const TA*)a, va, (const TB*)b, vb, total, coef_dev, \
+                     (TA*)ga, (TB*)gb)
+  LOSS_BY_PAIR(CALL);
+#undef CALL
+  CHECK_LAUNCH();
+}
+
+int cvvae_gauss_reg(int32_t dtype, const void* moments, const void* noise, void* z, int64_t B, int64_t C, int64_t S, void* workspace,
+                    float* kl_sum, void* stream) {
+  if (!moments || !z || !workspace || !kl_sum || B <= 0 || C <= 0 || S <= 0) return CVVAE_EINVAL;
+  if (!known_dtype(dtype)) return CVVAE_EUNSUPPORTED;
+  if (B >= (1 << 30) || C > (1LL << 40) / S || C * S > (1LL << 40) / B) return CVVAE_EUNSUPPORTED;
+  const long long CS = (long long)C * S, total = CS * B;
+  const int nblk = (int)blocks_for(total);
+  hipStream_t s = (hipStream_t)stream;
+#define CALL(T) \
+  hipLaunchKernelGGL(gauss_reg_kernel<T>, dim3(nblk), dim3(WG), 0, s, (const T*)moments, (const T*)noise, (T*)z, CS, total, (float*)workspace)
+  LOSS_BY_DTYPE(CALL);
+#undef CALL
+  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(WG), 0, s, (const float*)workspace, nblk, 0.5f, kl_sum);
+  CHECK_LAUNCH();
+}
+
+int cvvae_gauss_reg_bwd(int32_t dtype, const void* moments, const void* noise, const void* g_z, const float* coef_kl_dev,
+                        void* g_moments, int64_t B, int64_t C, int64_t S, void* stream) {
+  if (!moments || !coef_kl_dev || !g_moments || B <= 0 || C <= 0 || S <= 0) return CVVAE_EINVAL;
+  if (!known_dtype(dtype)) return CVVAE_EUNSUPPORTED;
+  if (B >= (1 << 30) || C > (1LL << 40) / S || C * S > (1LL << 40) / B) return CVVAE_EUNSUPPORTED;
+  const long long CS = (long long)C * S, total = CS * B;
+  const long long tiles = (total + TILE - 1) / TILE;
+  const int nblk = (int)(tiles < 65536 ? tiles : 65536);
+  hipStream_t s = (hipStream_t)stream;
+#define CALL(T) \
+  hipLaunchKernelGGL(gauss_reg_bwd_kernel<T>, dim3(nblk), dim3(WG), 0, s, (const T*)moments, (const T*)noise, (const T*)g_z, coef_kl_dev, \
+                     (T*)g_moments, CS, total)
+  LOSS_BY_DTYPE(CALL);
+#undef CALL
+  CHECK_LAUNCH();
+}
+
+}  // extern "C"

@@ -5,6 +5,7 @@ dtype torch.float16 or torch.bfloat16, on a ROCm device.  Nothing here computes 
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
+import ctypes
 import os
 
 import torch
@@ -1009,3 +1010,115 @@ def lpips_head_bwd(f0: torch.Tensor, f1: torch.Tensor, w: torch.Tensor, gout: to
     L.check(lib.cvvae_lpips_head_bwd(_dt(f0.dtype), f0.data_ptr(), f1.data_ptr(), w.data_ptr(), gout.data_ptr(), N, HW, C,
                                      g0.data_ptr() if g0 is not None else None, g1.data_ptr() if g1 is not None else None,
                                      _stream(f0)), "cvvae_lpips_head_bwd")
+
+
+# ---- the training loss around the networks (include/cvvae.h cvvae_reduce_sum / cvvae_gauss_reg; cvvae_amd/loss.py) ----
+TWO_OPERAND_OPS = (L.RED_ABS_DIFF, L.RED_SQ_DIFF)
+
+
+def _reduce_shape(a: torch.Tensor, b: Optional[torch.Tensor]) -> "L.ReduceShape":
+    """a (and b, of the same shape) as cvvae_reduce_shape: dimensions that are contiguous in BOTH operands are merged, the last
+    one with unit strides becomes the inner run, up to three strided dimensions stay outside -- views are read in place"""
+    sb = b.stride() if b is not None else a.stride()
+    dims = [[n, x, y] for n, x, y in zip(a.shape, a.stride(), sb) if n != 1]
+    merged = []
+    for d in dims:
+        if merged and merged[-1][1] == d[0] * d[1] and merged[-1][2] == d[0] * d[2]:
+            merged[-1] = [merged[-1][0] * d[0], d[1], d[2]]
+        else:
+            merged.append(d)
+    inner = 1
+    if merged and merged[-1][1] == 1 and merged[-1][2] == 1:
+        inner = merged.pop()[0]
+    if len(merged) > 3 or any(x < 0 or y < 0 for _, x, y in merged):
+        raise ValueError(f"cvvae_reduce_sum reads up to three strided dimensions over a contiguous run; got sizes {tuple(a.shape)} "
+                         f"with strides {tuple(a.stride())}" + (f" / {tuple(b.stride())}" if b is not None else ""))
+    merged = [[1, 0, 0]] * (3 - len(merged)) + merged
+    s = L.ReduceShape()
+    for i, (n, x, y) in enumerate(merged):
+        s.n[i], s.sa[i], s.sb[i] = n, x, y
+    s.L = inner
+    return s
+
+
+def _reduce_args(op: int, a: torch.Tensor, b: Optional[torch.Tensor]):
+    _need_gpu(a)
+    if (b is not None) != (op in TWO_OPERAND_OPS):
+        raise ValueError(f"cvvae_reduce_sum op {op} takes {'two operands' if op in TWO_OPERAND_OPS else 'one operand'}")
+    if a.numel() == 0:
+        raise ValueError("cvvae_reduce_sum: empty tensor")
+    if b is not None:
+        _need_gpu(b)
+        if b.shape != a.shape or b.device != a.device:
+            raise ValueError(f"cvvae_reduce_sum: operands of shapes {tuple(a.shape)} and {tuple(b.shape)} on {a.device} / {b.device}")
+    return _reduce_shape(a, b)
+
+
+def reduce_sum(op: int, a: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sum over all elements of f_op(a[, b]) (op: L.RED_*) -> 0-dim fp32 tensor; fp32 arithmetic, deterministic (no atomics).
+    a / b: fp16 / bf16 / fp32 independently, same shape, any strides the shape rule of _reduce_shape can describe."""
+    lib = L.load()
+    shape = _reduce_args(op, a, b)
+    ws = torch.empty(max(int(lib.cvvae_reduce_workspace_bytes(ctypes.byref(shape))), 16), dtype=torch.uint8, device=a.device)
+    out = torch.empty((), dtype=torch.float32, device=a.device)
+    L.check(lib.cvvae_reduce_sum(op, _dt(a.dtype), a.data_ptr(), _dt(b.dtype) if b is not None else L.F32,
+                                 b.data_ptr() if b is not None else None, ctypes.byref(shape), ws.data_ptr(), out.data_ptr(),
+                                 _stream(a)), "cvvae_reduce_sum")
+    return out
+
+
+def reduce_sum_bwd(op: int, a: torch.Tensor, b: Optional[torch.Tensor], coef: torch.Tensor, want_a: bool = True,
+                   want_b: bool = False) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """-> (ga, gb): coef * f_op'(a, b) shaped as a (contiguous) in a's dtype, and its negative in b's dtype (two-operand ops);
+    coef: a 0-dim fp32 DEVICE tensor (no host synchronisation)"""
+    lib = L.load()
+    shape = _reduce_args(op, a, b)
+    assert coef.dtype == torch.float32 and coef.numel() == 1 and coef.device == a.device
+    assert want_a or want_b
+    ga = torch.empty(a.shape, dtype=a.dtype, device=a.device) if want_a else None
+    gb = torch.empty(b.shape, dtype=b.dtype, device=b.device) if want_b else None
+    L.check(lib.cvvae_reduce_sum_bwd(op, _dt(a.dtype), a.data_ptr(), _dt(b.dtype) if b is not None else L.F32,
+                                     b.data_ptr() if b is not None else None, ctypes.byref(shape), coef.data_ptr(),
+                                     ga.data_ptr() if ga is not None else None, gb.data_ptr() if gb is not None else None,
+                                     _stream(a)), "cvvae_reduce_sum_bwd")
+    return ga, gb
+
+
+def _gauss_dims(moments: torch.Tensor) -> Tuple[int, int, int]:
+    _need_gpu(moments)
+    if moments.dim() < 3 or moments.shape[1] % 2 or not moments.is_contiguous():
+        raise ValueError(f"cvvae_gauss_reg takes contiguous moments [B, 2C, ...]; got {tuple(moments.shape)}")
+    B, C2 = moments.shape[:2]
+    return B, C2 // 2, moments.numel() // (B * C2)
+
+
+def gauss_reg(moments: torch.Tensor, noise: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """moments [B, 2C, ...] -> (z [B, C, ...] = mean + exp(0.5 clamp(logvar, -30, 20)) * noise, or mean when noise is None;
+    kl_sum: 0-dim fp32 = 0.5 sum(mean^2 + var - 1 - logvar) over everything).  noise: shaped and typed as z."""
+    lib = L.load()
+    B, C, S = _gauss_dims(moments)
+    z = torch.empty((B, C, *moments.shape[2:]), dtype=moments.dtype, device=moments.device)
+    if noise is not None:
+        assert noise.shape == z.shape and noise.dtype == z.dtype and noise.device == z.device and noise.is_contiguous()
+    shape = L.ReduceShape()
+    shape.n[0], shape.n[1], shape.n[2], shape.L = 1, 1, B, C * S
+    ws = torch.empty(max(int(lib.cvvae_reduce_workspace_bytes(ctypes.byref(shape))), 16), dtype=torch.uint8, device=z.device)
+    kl = torch.empty((), dtype=torch.float32, device=z.device)
+    L.check(lib.cvvae_gauss_reg(_dt(moments.dtype), moments.data_ptr(), noise.data_ptr() if noise is not None else None, z.data_ptr(),
+                                B, C, S, ws.data_ptr(), kl.data_ptr(), _stream(moments)), "cvvae_gauss_reg")
+    return z, kl
+
+
+def gauss_reg_bwd(moments: torch.Tensor, noise: Optional[torch.Tensor], g_z: Optional[torch.Tensor], coef_kl: torch.Tensor) -> torch.Tensor:
+    """-> g_moments shaped as moments: d mean = g_z + coef mean, d logvar = (g_z noise 0.5 std + coef 0.5 (var - 1)) inside clamp's
+    inclusive mask.  coef_kl: 0-dim fp32 DEVICE tensor = dL/d kl_sum; g_z None: only the KL term is back-propagated."""
+    lib = L.load()
+    B, C, S = _gauss_dims(moments)
+    for t in (noise, g_z):
+        assert t is None or (t.numel() == B * C * S and t.dtype == moments.dtype and t.device == moments.device and t.is_contiguous())
+    assert coef_kl.dtype == torch.float32 and coef_kl.numel() == 1 and coef_kl.device == moments.device
+    g = torch.empty_like(moments)
+    L.check(lib.cvvae_gauss_reg_bwd(_dt(moments.dtype), moments.data_ptr(), noise.data_ptr() if noise is not None else None,
+                                    g_z.data_ptr() if g_z is not None else None, coef_kl.data_ptr(), g.data_ptr(), B, C, S,
+                                    _stream(moments)), "cvvae_gauss_reg_bwd")
+    return g

@@ -475,6 +475,57 @@ int cvvae_lpips_head(int32_t dtype, const void* f0, const void* f1, const float*
 int cvvae_lpips_head_bwd(int32_t dtype, const void* f0, const void* f1, const float* w, const float* gout, int64_t N, int64_t HW,
                          int32_t C, void* g_f0, void* g_f1, void* stream);
 
+/*
+ * The training loss around the networks (cvvae_amd/loss.py; csrc/loss_kernels.hip): the pixel / NLL, KL and GAN terms of
+ * lvdm/modules/autoencoding/losses/discriminator_loss.py and the posterior of lvdm/modules/autoencoding/regularizers.  Additions to
+ * ABI 14: no existing entry point or struct changed, so the version number stays.
+ *
+ * cvvae_reduce_sum: out[0] = sum over all elements of f_op(a[, b]) as ONE fp32 scalar (overwritten, not accumulated).  An operand is
+ * n[0] x n[1] x n[2] runs of L contiguous elements, run (i0, i1, i2) starting at element i0 sa[0] + i1 sa[1] + i2 sa[2] (sb for b): a
+ * `[:, :, ::4]` frame slice of an NCDHW clip is read in place.  Strides are >= 0 (0 broadcasts); unused dimensions have n = 1.
+ * dtype_a and dtype_b are independently CVVAE_F16 / CVVAE_BF16 / CVVAE_F32; arithmetic and accumulation are fp32.  Two launches:
+ * per-workgroup partial sums into `workspace` (cvvae_reduce_workspace_bytes, pure host code), then one workgroup that merges them.
+ * The order of summation is a function of the logical element index alone and nothing is atomic: the same values give the same
+ * bits on every run, whatever the strides and the alignment.  Two-operand ops need b, unary ops need b == NULL (else CVVAE_EINVAL);
+ * an unknown op or dtype is CVVAE_EUNSUPPORTED.
+ * cvvae_reduce_sum_bwd: ga[i] = coef f_op'(a[i], b[i]) and / or gb[i] = -ga[i] (two-operand ops only), i the logical index: ga and gb
+ * are contiguous, in dtype_a / dtype_b; either may be NULL, not both.  coef is read from a DEVICE fp32 scalar.  |a - b|' is
+ * sign(a - b) with sign(0) = 0; the hinges' sub-gradient is 0 where the argument of relu is not > 0 (aten::threshold_backward).
+ */
+enum {
+  CVVAE_RED_ABS_DIFF = 0,     /* |a - b| */
+  CVVAE_RED_SQ_DIFF = 1,      /* (a - b)^2 */
+  CVVAE_RED_SQ = 2,           /* a^2 */
+  CVVAE_RED_IDENT = 3,        /* a */
+  CVVAE_RED_HINGE_NEG = 4,    /* relu(1 - a) */
+  CVVAE_RED_HINGE_POS = 5,    /* relu(1 + a) */
+  CVVAE_RED_SOFTPLUS_NEG = 6, /* softplus(-a)  (beta 1, threshold 20, as aten::softplus) */
+  CVVAE_RED_SOFTPLUS_POS = 7  /* softplus(a) */
+};
+typedef struct cvvae_reduce_shape {
+  int64_t n[3];  /* outer extents, slowest first */
+  int64_t L;     /* contiguous inner run, elements */
+  int64_t sa[3]; /* element strides of a's outer dimensions */
+  int64_t sb[3]; /* ... of b's (ignored by unary ops) */
+} cvvae_reduce_shape;
+size_t cvvae_reduce_workspace_bytes(const cvvae_reduce_shape* shape);
+int cvvae_reduce_sum(int32_t op, int32_t dtype_a, const void* a, int32_t dtype_b, const void* b, const cvvae_reduce_shape* shape,
+                     void* workspace, float* out, void* stream);
+int cvvae_reduce_sum_bwd(int32_t op, int32_t dtype_a, const void* a, int32_t dtype_b, const void* b, const cvvae_reduce_shape* shape,
+                         const float* coef_dev, void* ga, void* gb, void* stream);
+/*
+ * DiagonalGaussianDistribution (lvdm/modules/distributions/distributions.py:24-52) in one pass.  moments [B][2C][S] (S = t h w or
+ * h w) is chunked at channel C into mean and logvar, logvar clamped to [-30, 20]; z [B][C][S] = mean + exp(0.5 logvar) noise
+ * (noise [B][C][S], or NULL: z = mean); kl_sum[0] = 0.5 sum (mean^2 + exp(logvar) - 1 - logvar) over EVERYTHING, through the two-stage
+ * reduction above: workspace >= cvvae_reduce_workspace_bytes of {n = {1, 1, B}, L = C S}.  All tensors of `dtype`, fp32 arithmetic.
+ * cvvae_gauss_reg_bwd: g_moments [B][2C][S]:  d mean = g_z + coef mean,  d logvar = (g_z noise 0.5 std + coef 0.5 (var - 1)) where
+ * -30 <= the RAW logvar <= 20 (clamp's inclusive mask), else 0.  coef = dL/d kl_sum, a DEVICE fp32 scalar; g_z (and noise) may be NULL.
+ */
+int cvvae_gauss_reg(int32_t dtype, const void* moments, const void* noise, void* z, int64_t B, int64_t C, int64_t S, void* workspace,
+                    float* kl_sum, void* stream);
+int cvvae_gauss_reg_bwd(int32_t dtype, const void* moments, const void* noise, const void* g_z, const float* coef_kl_dev,
+                        void* g_moments, int64_t B, int64_t C, int64_t S, void* stream);
+
 int cvvae_abi_version(void);
 /* name of the kernel instance cvvae_conv_fwd would launch for d (for profiling reports); NULL if unsupported */
 const char* cvvae_conv_kernel_name(const cvvae_conv_desc* d);
