@@ -115,6 +115,10 @@ PROTOTYPES = {
     "cvvae_reduce_sum_bwd": (_i32, [_i32, _i32, _vp, _i32, _vp, ctypes.POINTER(ReduceShape), _vp, _vp, _vp, _vp]),
     "cvvae_gauss_reg": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "cvvae_gauss_reg_bwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    "cvvae_avgpool3d_down": (_i32, [_i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "cvvae_avgpool3d_down_bwd": (_i32, [_i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "cvvae_gn_leaky_apply": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _f32, _vp]),
+    "cvvae_leaky_bwd": (_i32, [_i32, _vp, _vp, _vp, _i64, _f32, _vp]),
 }
 
 _lib = None
@@ -122,7 +126,7 @@ _lib = None
 
 # translation units whose kernels only run in training (weight gradients, channel sums, their reductions): no launch of an
 # encode / decode step comes from them, so the counters of the inference bench do not go stale when they change
-TRAINING_ONLY_SOURCES = ("wgrad_kernel.hip", "loss_kernels.hip")
+TRAINING_ONLY_SOURCES = ("wgrad_kernel.hip", "loss_kernels.hip", "disc_kernels.hip")
 
 
 def source_fingerprint() -> str:

@@ -322,6 +322,8 @@ __global__ void pack_upfold_xp_kernel(const float* __restrict__ src, int Cout, i
 // ---------------------------------------------------------------------------------------------------------
 // GroupNorm statistics.  Stage 1: grid (nsplit, rows); each block reduces a slab of pixels for all channels
 // with Welford/Chan updates on 4-channel quads; stage 2 merges the slabs and emits the affine table.
+// SUB = channels per statistics slot of a lane's 8 channels: 4 (groups of whole quads), or 2 for groups of 2 or 6 channels
+// (GroupNorm(32, 64) of the discriminator) -- the same arithmetic on pairs.
 // ---------------------------------------------------------------------------------------------------------
 struct WStat {
   float n, mean, m2;
@@ -336,7 +338,7 @@ __device__ __forceinline__ void chan_merge(WStat& a, const WStat& b) {
   a.n = n;
 }
 
-template <typename T>
+template <typename T, int SUB = 4>
 __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x, long long S, int C, long long ps,
                                                          int G, int nsplit, float* __restrict__ ws) {
   const int split = blockIdx.x, row = blockIdx.y;
@@ -348,7 +350,10 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
   const long long p0 = (long long)split * per;
   long long p1 = p0 + per;
   if (p1 > S) p1 = S;
-  WStat st[2] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+  constexpr int NS = 8 / SUB;  // slots per lane
+  WStat st[NS];
+#pragma unroll
+  for (int h = 0; h < NS; ++h) st[h] = {0.f, 0.f, 0.f};
   if (tid < cv * ppp) {
     const T* base = x + ((long long)row * S) * ps + myv * 8;
     long long px = p0 + mypl;
@@ -363,20 +368,25 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
 #pragma unroll
       for (int i = 0; i < U; ++i) unraw8<T>(u[i], f[i]);
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
+      for (int h = 0; h < NS; ++h) {
         float sum = 0.f;
 #pragma unroll
-        for (int i = 0; i < U; ++i) sum += (f[i][h * 4 + 0] + f[i][h * 4 + 1]) + (f[i][h * 4 + 2] + f[i][h * 4 + 3]);
-        const float mb = sum * (1.0f / (4 * U));
+        for (int i = 0; i < U; ++i) {
+          if constexpr (SUB == 4)
+            sum += (f[i][h * 4 + 0] + f[i][h * 4 + 1]) + (f[i][h * 4 + 2] + f[i][h * 4 + 3]);
+          else
+            sum += f[i][h * 2 + 0] + f[i][h * 2 + 1];
+        }
+        const float mb = sum * (1.0f / (SUB * U));
         float m2b = 0.f;
 #pragma unroll
         for (int i = 0; i < U; ++i)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float d = f[i][h * 4 + j] - mb;
+          for (int j = 0; j < SUB; ++j) {
+            const float d = f[i][h * SUB + j] - mb;
             m2b += d * d;
           }
-        WStat q = {(float)(4 * U), mb, m2b};
+        WStat q = {(float)(SUB * U), mb, m2b};
         chan_merge(st[h], q);
       }
     }
@@ -384,28 +394,36 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
       float f[8];
       ld8<T>(base + px * ps, f);
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const float a = f[h * 4 + 0], b = f[h * 4 + 1], c = f[h * 4 + 2], d = f[h * 4 + 3];
-        const float mb = (a + b + c + d) * 0.25f;
-        const float m2b = (a - mb) * (a - mb) + (b - mb) * (b - mb) + (c - mb) * (c - mb) + (d - mb) * (d - mb);
-        WStat q = {4.f, mb, m2b};
-        chan_merge(st[h], q);
+      for (int h = 0; h < NS; ++h) {
+        if constexpr (SUB == 4) {
+          const float a = f[h * 4 + 0], b = f[h * 4 + 1], c = f[h * 4 + 2], d = f[h * 4 + 3];
+          const float mb = (a + b + c + d) * 0.25f;
+          const float m2b = (a - mb) * (a - mb) + (b - mb) * (b - mb) + (c - mb) * (c - mb) + (d - mb) * (d - mb);
+          WStat q = {4.f, mb, m2b};
+          chan_merge(st[h], q);
+        } else {
+          const float a = f[h * 2 + 0], b = f[h * 2 + 1];
+          const float mb = (a + b) * 0.5f;
+          const float m2b = (a - mb) * (a - mb) + (b - mb) * (b - mb);
+          WStat q = {2.f, mb, m2b};
+          chan_merge(st[h], q);
+        }
       }
     }
   }
-  __shared__ WStat sh[256 * 2];
-  sh[tid * 2 + 0] = st[0];
-  sh[tid * 2 + 1] = st[1];
+  __shared__ WStat sh[256 * NS];
+#pragma unroll
+  for (int h = 0; h < NS; ++h) sh[tid * NS + h] = st[h];
   __syncthreads();
   if (tid < G) {
-    const int cpg = C / G;        // channels per group (multiple of 4)
-    const int qpg = cpg >> 2;     // quads per group
+    const int cpg = C / G;        // channels per group (multiple of SUB)
+    const int qpg = cpg / SUB;    // slots (quads / pairs) per group
     WStat acc = {0.f, 0.f, 0.f};
-    const int q0 = tid * qpg;     // first quad index (over channels) of this group
+    const int q0 = tid * qpg;     // first slot index (over channels) of this group
     for (int pl = 0; pl < ppp; ++pl)
       for (int q = q0; q < q0 + qpg; ++q) {
-        const int v = q >> 1, h = q & 1;
-        chan_merge(acc, sh[(pl * cv + v) * 2 + h]);
+        const int v = q / NS, h = q % NS;
+        chan_merge(acc, sh[(pl * cv + v) * NS + h]);
       }
     float* o = ws + (((long long)row * nsplit + split) * G + tid) * 3;
     o[0] = acc.n;
@@ -645,7 +663,7 @@ __device__ __forceinline__ void gn_bwd_load_tab(GnBwdTab& t, const float* __rest
 
 // PARAMS: also the per-channel sums of the affine gradients  d beta = sum gy act'(a),  d gamma = sum gy act'(a) xh  (the kernel forms
 // gy act'(a) anyway: training the norm costs no extra pass over x and gy), one [C][2] table per (row, split) in `wsp`
-template <typename T, bool PARAMS = false>
+template <typename T, bool PARAMS = false, int SUB = 4>  // SUB: channels per group-sum slot, as in gn_partial_kernel
 __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ gy, long long S, int C,
                                                             int G, int nsplit, const float* __restrict__ rs,
                                                             const float* __restrict__ nm, const float* __restrict__ gamma,
@@ -660,7 +678,10 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict_
   if (p1 > S) p1 = S;
   GnBwdTab t;
   gn_bwd_load_tab(t, rs, nm, gamma, beta, row, C, myv * 8);
-  float a1[2] = {0.f, 0.f}, a2[2] = {0.f, 0.f};
+  constexpr int NS = 8 / SUB;
+  float a1[NS], a2[NS];
+#pragma unroll
+  for (int h = 0; h < NS; ++h) a1[h] = a2[h] = 0.f;
   float pb[PARAMS ? 8 : 1], pg[PARAMS ? 8 : 1];
 #pragma unroll
   for (int j = 0; j < (PARAMS ? 8 : 1); ++j) pb[j] = pg[j] = 0.f;
@@ -690,8 +711,8 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict_
         const float a = __builtin_fmaf(xh, t.ga[j], t.be[j]);
         const float gact = g[u][j] * (silu ? silu_grad_f(a) : 1.0f);
         const float gh = gact * t.ga[j];
-        a1[j >> 2] += gh;
-        a2[j >> 2] += gh * xh;
+        a1[j / SUB] += gh;
+        a2[j / SUB] += gh * xh;
         if constexpr (PARAMS) {
           pb[j] += gact;
           pg[j] += gact * xh;
@@ -718,18 +739,21 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict_
       o[1] = s2;
     }
   }
-  __shared__ float sh1[256][2], sh2[256][2];
-  sh1[tid][0] = a1[0]; sh1[tid][1] = a1[1];
-  sh2[tid][0] = a2[0]; sh2[tid][1] = a2[1];
+  __shared__ float sh1[256][NS], sh2[256][NS];
+#pragma unroll
+  for (int h = 0; h < NS; ++h) {
+    sh1[tid][h] = a1[h];
+    sh2[tid][h] = a2[h];
+  }
   __syncthreads();
-  if (tid < G) {  // group tid: its channel quads q, every pixel lane, in index order
-    const int qpg = (C / G) >> 2;
+  if (tid < G) {  // group tid: its channel slots (quads / pairs) q, every pixel lane, in index order
+    const int qpg = (C / G) / SUB;
     float s1 = 0.f, s2 = 0.f;
     for (int q = tid * qpg; q < (tid + 1) * qpg; ++q)
       for (int pl = 0; pl < ppp; ++pl) {
-        const int th = pl * cv + (q >> 1);
-        s1 += sh1[th][q & 1];
-        s2 += sh2[th][q & 1];
+        const int th = pl * cv + q / NS;
+        s1 += sh1[th][q % NS];
+        s2 += sh2[th][q % NS];
       }
     float* o = ws + (((long long)row * nsplit + split) * G + tid) * 2;
     o[0] = s1;
@@ -737,7 +761,7 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict_
   }
 }
 
-template <typename T>
+template <typename T, int SUB = 4>
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ gy,
                                                            const T* __restrict__ add, T* __restrict__ out, long long S, int C, int G,
                                                            int nsplit, const float* __restrict__ rs, const float* __restrict__ nm,
@@ -774,7 +798,13 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__
   GnBwdTab t;
   gn_bwd_load_tab(t, rs, nm, gamma, beta, row, C, myv * 8);
   const int cpg = C / G;
-  const float m1a = c1[(myv * 8) / cpg], m2a = c2[(myv * 8) / cpg], m1b = c1[(myv * 8 + 4) / cpg], m2b = c2[(myv * 8 + 4) / cpg];
+  constexpr int NS = 8 / SUB;
+  float m1[NS], m2[NS];  // the group means of my channel slots
+#pragma unroll
+  for (int h = 0; h < NS; ++h) {
+    m1[h] = c1[(myv * 8 + h * SUB) / cpg];
+    m2[h] = c2[(myv * 8 + h * SUB) / cpg];
+  }
   const long long nvec = S * cv, base = (long long)row * S * C;
   for (long long v = (long long)blockIdx.x * 256 + tid; v < nvec; v += (long long)gridDim.x * 256) {
     const long long off = base + v * 8;  // v = pixel * cv + myv
@@ -787,7 +817,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__
       const float xh = __builtin_fmaf(f[j], t.rs[j], t.nm[j]);
       const float a = __builtin_fmaf(xh, t.ga[j], t.be[j]);
       const float gh = g[j] * (silu ? silu_grad_f(a) : 1.0f) * t.ga[j];
-      const float r = t.rs[j] * (gh - (j < 4 ? m1a : m1b) - xh * (j < 4 ? m2a : m2b));
+      const float r = t.rs[j] * (gh - m1[j / SUB] - xh * m2[j / SUB]);
       f[j] = add ? r + ad[j] : r;
     }
     st8<T>(out + off, f);
@@ -868,22 +898,22 @@ __global__ __launch_bounds__(256) void gn_params_final_kernel(const float* __res
   }
 }
 
-template <typename T>
+template <typename T, int SUB = 4>
 static void gn_bwd_launch(const void* x, const void* gy, const void* add, int rows, long long S, int C, int G, const float* rs,
                           const float* nm, const float* gamma, const float* beta, int silu, void* gx, float* ws, hipStream_t s,
                           float* dgamma = nullptr, float* dbeta = nullptr) {
   const int nsplit = gn_bwd_splits(S);
   if (dgamma) {  // training the norm: the affine sums ride on the reduction pass (tables behind the group sums in the workspace)
     float* wsp = ws + (long long)rows * nsplit * G * 2;
-    hipLaunchKernelGGL((gn_bwd_reduce_kernel<T, true>), dim3(nsplit, rows), dim3(256), 0, s, (const T*)x, (const T*)gy, S, C, G, nsplit,
+    hipLaunchKernelGGL((gn_bwd_reduce_kernel<T, true, SUB>), dim3(nsplit, rows), dim3(256), 0, s, (const T*)x, (const T*)gy, S, C, G, nsplit,
                        rs, nm, gamma, beta, silu, ws, wsp);
     hipLaunchKernelGGL(gn_params_final_kernel, dim3((C + 31) / 32), dim3(256), 0, s, (const float*)wsp, rows * nsplit, C, dbeta, dgamma);
   } else
-  hipLaunchKernelGGL(gn_bwd_reduce_kernel<T>, dim3(nsplit, rows), dim3(256), 0, s, (const T*)x, (const T*)gy, S, C, G, nsplit, rs, nm,
+  hipLaunchKernelGGL((gn_bwd_reduce_kernel<T, false, SUB>), dim3(nsplit, rows), dim3(256), 0, s, (const T*)x, (const T*)gy, S, C, G, nsplit, rs, nm,
                      gamma, beta, silu, ws);
   long long blocks = (S * (C / 8) + 255) / 256;
   if (blocks > 2048) blocks = 2048;  // grid-stride beyond 8 blocks per CU and row
-  hipLaunchKernelGGL(gn_bwd_apply_kernel<T>, dim3((unsigned)blocks, rows), dim3(256), 0, s, (const T*)x, (const T*)gy, (const T*)add,
+  hipLaunchKernelGGL((gn_bwd_apply_kernel<T, SUB>), dim3((unsigned)blocks, rows), dim3(256), 0, s, (const T*)x, (const T*)gy, (const T*)add,
                      (T*)gx, S, C, G, nsplit, rs, nm, gamma, beta, silu, ws);
 }
 
@@ -1461,20 +1491,28 @@ int cvvae_gn_stats(int32_t dtype, const void* x, int32_t rows, int64_t S, int32_
                    float eps, const float* gamma, const float* beta, float* scale, float* shift, void* workspace,
                    void* stream) {
   if (!x || !gamma || !beta || !scale || !shift || !workspace || rows <= 0 || S <= 0) return CVVAE_EINVAL;
-  if (groups <= 0 || groups > 32 || C % groups || (C / groups) % 4 || C % 8 || C > 2048 || pix_stride % 8) return CVVAE_EUNSUPPORTED;
+  if (groups <= 0 || groups > 32 || C % groups || (C / groups) % 2 || C % 8 || C > 2048 || pix_stride % 8) return CVVAE_EUNSUPPORTED;
   const int nsplit = gn_nsplit(S);
   hipStream_t s = (hipStream_t)stream;
+  const bool quads = (C / groups) % 4 == 0;  // else pairs: groups of 2 or 6 channels
+#define GN_PARTIAL(T) \
+  do { \
+    if (quads) \
+      hipLaunchKernelGGL((gn_partial_kernel<T, 4>), dim3(nsplit, rows), dim3(256), 0, s, (const T*)x, (long long)S, C, \
+                         (long long)pix_stride, groups, nsplit, (float*)workspace); \
+    else \
+      hipLaunchKernelGGL((gn_partial_kernel<T, 2>), dim3(nsplit, rows), dim3(256), 0, s, (const T*)x, (long long)S, C, \
+                         (long long)pix_stride, groups, nsplit, (float*)workspace); \
+  } while (0)
   if (dtype == CVVAE_BF16)
-    hipLaunchKernelGGL(gn_partial_kernel<__bf16>, dim3(nsplit, rows), dim3(256), 0, s, (const __bf16*)x, (long long)S, C,
-                       (long long)pix_stride, groups, nsplit, (float*)workspace);
+    GN_PARTIAL(__bf16);
   else if (dtype == CVVAE_F16)
-    hipLaunchKernelGGL(gn_partial_kernel<_Float16>, dim3(nsplit, rows), dim3(256), 0, s, (const _Float16*)x, (long long)S, C,
-                       (long long)pix_stride, groups, nsplit, (float*)workspace);
+    GN_PARTIAL(_Float16);
   else if (dtype == CVVAE_F32)
-    hipLaunchKernelGGL(gn_partial_kernel<float>, dim3(nsplit, rows), dim3(256), 0, s, (const float*)x, (long long)S, C,
-                       (long long)pix_stride, groups, nsplit, (float*)workspace);
+    GN_PARTIAL(float);
   else
     return CVVAE_EINVAL;
+#undef GN_PARTIAL
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(rows), dim3(256), 0, s, (const float*)workspace, nsplit, groups, C, eps, gamma,
                      beta, scale, shift);
   CHECK_LAUNCH();
@@ -1526,19 +1564,28 @@ int64_t cvvae_gn_bwd_params_workspace_bytes(int32_t rows, int32_t groups, int64_
   return (int64_t)rows * gn_bwd_splits(S) * (groups + C) * 2 * (int64_t)sizeof(float);
 }
 
+// group sums on channel quads where the groups are made of them, on pairs otherwise (groups of 2 or 6 channels)
+#define GN_BWD_LAUNCH(T, DG, DB) \
+  do { \
+    if ((C / groups) % 4 == 0) \
+      gn_bwd_launch<T, 4>(x, gy, add, rows, S, C, groups, rstd, nmean, gamma, beta, silu, gx, (float*)workspace, s, DG, DB); \
+    else \
+      gn_bwd_launch<T, 2>(x, gy, add, rows, S, C, groups, rstd, nmean, gamma, beta, silu, gx, (float*)workspace, s, DG, DB); \
+  } while (0)
+
 int cvvae_gn_bwd_input_params(int32_t dtype, const void* x, const void* gy, const void* add, int32_t rows, int64_t S, int32_t C,
                               int32_t groups, const float* rstd, const float* nmean, const float* gamma, const float* beta,
                               int32_t silu, void* gx, float* dgamma, float* dbeta, void* workspace, void* stream) {
   if (!x || !gy || !gx || !rstd || !nmean || !gamma || !beta || !workspace || !dgamma || !dbeta || rows <= 0 || S <= 0 || C <= 0)
     return CVVAE_EINVAL;
-  if (groups <= 0 || groups > 64 || C % groups || (C / groups) % 4 || C % 8 || C > 2048 || 256 % (C / 8)) return CVVAE_EUNSUPPORTED;
+  if (groups <= 0 || groups > 64 || C % groups || (C / groups) % 2 || C % 8 || C > 2048 || 256 % (C / 8)) return CVVAE_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   if (dtype == CVVAE_BF16)
-    gn_bwd_launch<__bf16>(x, gy, add, rows, S, C, groups, rstd, nmean, gamma, beta, silu, gx, (float*)workspace, s, dgamma, dbeta);
+    GN_BWD_LAUNCH(__bf16, dgamma, dbeta);
   else if (dtype == CVVAE_F16)
-    gn_bwd_launch<_Float16>(x, gy, add, rows, S, C, groups, rstd, nmean, gamma, beta, silu, gx, (float*)workspace, s, dgamma, dbeta);
+    GN_BWD_LAUNCH(_Float16, dgamma, dbeta);
   else if (dtype == CVVAE_F32)
-    gn_bwd_launch<float>(x, gy, add, rows, S, C, groups, rstd, nmean, gamma, beta, silu, gx, (float*)workspace, s, dgamma, dbeta);
+    GN_BWD_LAUNCH(float, dgamma, dbeta);
   else
     return CVVAE_EINVAL;
   CHECK_LAUNCH();
@@ -1548,15 +1595,15 @@ int cvvae_gn_bwd_input(int32_t dtype, const void* x, const void* gy, const void*
                        int32_t groups, const float* rstd, const float* nmean, const float* gamma, const float* beta, int32_t silu,
                        void* gx, void* workspace, void* stream) {
   if (!x || !gy || !gx || !rstd || !nmean || !gamma || !beta || !workspace || rows <= 0 || S <= 0 || C <= 0) return CVVAE_EINVAL;
-  // 8-channel vectors that tile a 256-thread block; channel quads inside one group
-  if (groups <= 0 || groups > 64 || C % groups || (C / groups) % 4 || C % 8 || C > 2048 || 256 % (C / 8)) return CVVAE_EUNSUPPORTED;
+  // 8-channel vectors that tile a 256-thread block; channel quads (or pairs) inside one group
+  if (groups <= 0 || groups > 64 || C % groups || (C / groups) % 2 || C % 8 || C > 2048 || 256 % (C / 8)) return CVVAE_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   if (dtype == CVVAE_BF16)
-    gn_bwd_launch<__bf16>(x, gy, add, rows, S, C, groups, rstd, nmean, gamma, beta, silu, gx, (float*)workspace, s);
+    GN_BWD_LAUNCH(__bf16, nullptr, nullptr);
   else if (dtype == CVVAE_F16)
-    gn_bwd_launch<_Float16>(x, gy, add, rows, S, C, groups, rstd, nmean, gamma, beta, silu, gx, (float*)workspace, s);
+    GN_BWD_LAUNCH(_Float16, nullptr, nullptr);
   else if (dtype == CVVAE_F32)
-    gn_bwd_launch<float>(x, gy, add, rows, S, C, groups, rstd, nmean, gamma, beta, silu, gx, (float*)workspace, s);
+    GN_BWD_LAUNCH(float, nullptr, nullptr);
   else
     return CVVAE_EINVAL;
   CHECK_LAUNCH();

@@ -582,11 +582,11 @@ def gn_bwd_input_params(x: torch.Tensor, gy: torch.Tensor, tabs: Tuple[torch.Ten
     assert rs.dtype == torch.float32 and tuple(rs.shape) == (rows, C) and rs.is_contiguous() and nm.is_contiguous()
     if add is not None:
         assert add.shape == x.shape and add.dtype == x.dtype and add.is_contiguous()
-    if C % groups or (C // groups) % 4 or C % 8 or C > 2048 or 256 % (C // 8):
+    if C % groups or (C // groups) % 2 or C % 8 or C > 2048 or 256 % (C // 8):
         # (both GroupNorm backward kernels map a 256-thread block onto whole rows of 8-channel lanes; the model classes admit only
         #  widths of 128 * 2^k -- modeling._channel_constraints -- so this is a caller error, reported before the launch)
         raise ValueError(f"GroupNorm backward: C = {C} with {groups} groups is not a width the kernels take (C/8 must divide 256, "
-                         f"channels per group a multiple of 4, C <= 2048)")
+                         f"channels per group even, C <= 2048)")
     out = torch.empty_like(x)
     dg = torch.empty(C, dtype=torch.float32, device=x.device)
     db = torch.empty(C, dtype=torch.float32, device=x.device)
@@ -1122,3 +1122,78 @@ def gauss_reg_bwd(moments: torch.Tensor, noise: Optional[torch.Tensor], g_z: Opt
                                     g_z.data_ptr() if g_z is not None else None, coef_kl.data_ptr(), g.data_ptr(), B, C, S,
                                     _stream(moments)), "cvvae_gauss_reg_bwd")
     return g
+
+
+def _ndhwc(t: torch.Tensor, what: str):
+    _need_gpu(t)
+    if t.dim() != 5 or not t.is_contiguous():
+        raise ValueError(f"{what}: a contiguous NDHWC tensor [B, T, H, W, C] is required; got shape {tuple(t.shape)}, strides {t.stride()}")
+
+
+def avgpool3d_down_shape(shape) -> Tuple[int, int, int, int, int]:
+    """[B, T, H, W, C] -> the shape of ResnetBlockDown3D's downsample: T rounded up to even, then every extent halved"""
+    B, T, H, W, C = shape
+    return (B, (T + (T & 1)) // 2, H // 2, W // 2, C)
+
+
+def avgpool3d_down(x: torch.Tensor) -> torch.Tensor:
+    """ResnetBlockDown3D's downsample on x [B,T,H,W,C] (cvvae_avgpool3d_down): an odd T gets its first frame duplicated in front
+    (never materialised), then avg_pool3d(2, 2): [B, ceil(T/2), H//2, W//2, C]"""
+    lib = L.load()
+    _ndhwc(x, "avgpool3d_down")
+    B, T, H, W, C = x.shape
+    out = torch.empty(avgpool3d_down_shape(x.shape), dtype=x.dtype, device=x.device)
+    L.check(lib.cvvae_avgpool3d_down(_dt(x.dtype), x.data_ptr(), out.data_ptr(), B, T, H, W, C, _stream(x)), "cvvae_avgpool3d_down")
+    return out
+
+
+def avgpool3d_down_bwd(gy: torch.Tensor, shape) -> torch.Tensor:
+    """adjoint of avgpool3d_down for an input of `shape` [B,T,H,W,C]: gy [B, ceil(T/2), H//2, W//2, C] -> gx of that shape, every
+    element written (cvvae_avgpool3d_down_bwd)"""
+    lib = L.load()
+    _ndhwc(gy, "avgpool3d_down_bwd")
+    B, T, H, W, C = (int(s) for s in shape)
+    if tuple(gy.shape) != avgpool3d_down_shape((B, T, H, W, C)):
+        raise ValueError(f"avgpool3d_down_bwd: gy {tuple(gy.shape)} is not the pooled shape of {(B, T, H, W, C)}")
+    out = torch.empty((B, T, H, W, C), dtype=gy.dtype, device=gy.device)
+    L.check(lib.cvvae_avgpool3d_down_bwd(_dt(gy.dtype), gy.data_ptr(), out.data_ptr(), B, T, H, W, C, _stream(gy)),
+            "cvvae_avgpool3d_down_bwd")
+    return out
+
+
+def gn_leaky_apply(x: torch.Tensor, gn: Optional[Tuple[torch.Tensor, torch.Tensor]], slope: float = 0.2,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """leaky_relu(x * scale + shift, slope) once per element (cvvae_gn_leaky_apply): x [B,T,H,W,C], gn = (scale, shift) fp32 tables
+    [B, C] of gn_stats / gn_finalize, or None for the bare LeakyReLU.  out = x runs in place."""
+    lib = L.load()
+    _ndhwc(x, "gn_leaky_apply")
+    B, T, H, W, C = x.shape
+    sc = sh = None
+    if gn is not None:
+        sc, sh = gn
+        if sc.dtype != torch.float32 or sh.dtype != torch.float32 or tuple(sc.shape) != (B, C) or tuple(sh.shape) != (B, C) \
+                or not sc.is_contiguous() or not sh.is_contiguous():
+            raise ValueError(f"gn_leaky_apply: the tables must be contiguous fp32 [{B}, {C}]")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+        raise ValueError("gn_leaky_apply: out must be a contiguous tensor like x")
+    L.check(lib.cvvae_gn_leaky_apply(_dt(x.dtype), x.data_ptr(), sc.data_ptr() if sc is not None else None,
+                                     sh.data_ptr() if sh is not None else None, out.data_ptr(), B, T * H * W, C, slope, _stream(x)),
+            "cvvae_gn_leaky_apply")
+    return out
+
+
+def leaky_bwd(y: torch.Tensor, gy: torch.Tensor, slope: float = 0.2, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gy where the LeakyReLU's OUTPUT y is positive, slope * gy elsewhere (cvvae_leaky_bwd).  out = gy runs in place."""
+    lib = L.load()
+    _need_gpu(y)
+    if not y.is_contiguous() or not gy.is_contiguous() or gy.shape != y.shape or gy.dtype != y.dtype or gy.device != y.device:
+        raise ValueError("leaky_bwd: y and gy must be contiguous tensors of one shape, dtype and device")
+    if out is None:
+        out = torch.empty_like(gy)
+    elif out.shape != y.shape or out.dtype != y.dtype or out.device != y.device or not out.is_contiguous():
+        raise ValueError("leaky_bwd: out must be a contiguous tensor like gy")
+    L.check(lib.cvvae_leaky_bwd(_dt(y.dtype), y.data_ptr(), gy.data_ptr(), out.data_ptr(), y.numel(), slope, _stream(y)),
+            "cvvae_leaky_bwd")
+    return out

@@ -265,6 +265,7 @@ int cvvae_gn_finalize_frames(const float* partials, int32_t rows, int32_t frames
  * models/vae_models3d_sd3.py:150,315, models/vae_models.py:192-195, and the per-frame group_norm of the attention
  * blocks (rows = B*T, S = H*W).  x is [rows][S][C] (pix_stride elements per pixel); biased variance; fp32 Chan merge.
  *   scale[row,c] = gamma[c]*rstd(row,g(c)),  shift[row,c] = beta[c] - mean(row,g(c))*scale[row,c]
+ * Constraints: C % 8 == 0, C <= 2048, groups <= 32, (C / groups) % 2 == 0 (else CVVAE_EUNSUPPORTED).
  * workspace: cvvae_gn_workspace_bytes(rows, groups, S) bytes.
  */
 size_t cvvae_gn_workspace_bytes(int32_t rows, int32_t groups, int64_t S);
@@ -297,7 +298,7 @@ int cvvae_gn_silu_apply(int32_t dtype, const void* x, int32_t rows, int64_t S, i
  * cvvae_gn_finalize / cvvae_gn_stats produce with gamma = 1, beta = 0 (scale = rstd, shift = -mean * rstd); gamma / beta [C] the
  * module's affine parameters.  Statistics are taken per row over its S pixels and C / groups channels.  Deterministic (two passes,
  * partial sums merged in index order).  workspace: cvvae_gn_bwd_workspace_bytes(rows, groups, S) bytes.
- * Constraints: C % 8 == 0, (C / groups) % 4 == 0, 256 % (C / 8) == 0, groups <= 64 (else CVVAE_EUNSUPPORTED).
+ * Constraints: C % 8 == 0, (C / groups) % 2 == 0, 256 % (C / 8) == 0, groups <= 64 (else CVVAE_EUNSUPPORTED).
  */
 int64_t cvvae_gn_bwd_workspace_bytes(int32_t rows, int32_t groups, int64_t S);
 int cvvae_gn_bwd_input(int32_t dtype, const void* x, const void* gy, const void* add, int32_t rows, int64_t S, int32_t C,
@@ -525,6 +526,37 @@ int cvvae_gauss_reg(int32_t dtype, const void* moments, const void* noise, void*
                     float* kl_sum, void* stream);
 int cvvae_gauss_reg_bwd(int32_t dtype, const void* moments, const void* noise, const void* g_z, const float* coef_kl_dev,
                         void* g_moments, int64_t B, int64_t C, int64_t S, void* stream);
+
+/*
+ * The non-convolution passes of the 3-D PatchGAN discriminator (models/discriminator.py:184-341; cvvae_amd/disc_ops.py;
+ * csrc/disc_kernels.hip) and their adjoints.  Additions to ABI 14: no existing entry point or struct changed, so the version number
+ * stays.  NDHWC tensors [B][T][H][W][C] of `dtype` (CVVAE_F16 / CVVAE_BF16 / CVVAE_F32), contiguous, 16-byte aligned, C % 8 == 0
+ * (else CVVAE_EUNSUPPORTED); fp32 arithmetic, one rounding to the storage dtype; every output element has one writer and nothing is
+ * atomic: the same inputs give the same bits.
+ *
+ * cvvae_avgpool3d_down: ResnetBlockDown3D's downsample (discriminator.py:240-243, 250-253): when T is odd the first frame is
+ * duplicated in front (torch.cat([h[:, :, :1], h], 2)), then avg_pool3d(kernel 2, stride 2).  y is [B][To][Ho][Wo][C], To = (T + (T & 1)) / 2,
+ * Ho = H / 2, Wo = W / 2 (floored: an odd last row / column is dropped).  Output frame t' averages padded frames 2t' and 2t' + 1; padded
+ * frame p is stored frame p (T even) or max(p - 1, 0) (T odd) -- the duplicate is never materialised.  The 8 values are summed in fp32
+ * (pairwise), multiplied by 0.125 and rounded once.  H < 2, W < 2 or an extent <= 0: CVVAE_EINVAL.
+ * cvvae_avgpool3d_down_bwd: its adjoint as a gather: gx (the input's shape, every element written) = 0.125 gy of the output element
+ * the input element went into; 0.25 gy for frame 0 of an odd T (it enters output frame 0 twice); 0 for a dropped row / column.
+ */
+int cvvae_avgpool3d_down(int32_t dtype, const void* x, void* y, int64_t B, int32_t T, int32_t H, int32_t W, int32_t C, void* stream);
+int cvvae_avgpool3d_down_bwd(int32_t dtype, const void* gy, void* gx, int64_t B, int32_t T, int32_t H, int32_t W, int32_t C,
+                             void* stream);
+/*
+ * cvvae_gn_leaky_apply: Normalize(c) + nn.LeakyReLU(slope, True) (discriminator.py:316-317, 330-331) in one pass:
+ * v = fma(x, scale[row][c], shift[row][c]),  y = v > 0 ? v : slope v.  x, y: [rows][per_row][C]; scale / shift: the fp32 tables [rows][C]
+ * of cvvae_gn_stats / cvvae_gn_finalize (per_row = T H W pixels for the 5-D GroupNorm).  scale == shift == NULL: the bare LeakyReLU
+ * (discriminator.py:302), v = x; exactly one of them NULL: CVVAE_EINVAL.  y == x (in place) is allowed.
+ * cvvae_leaky_bwd: gv = y > 0 ? gy : slope gy over n_elems elements, the mask taken from the activation's OUTPUT y (as autograd does for
+ * the in-place module; slope > 0 is required for that, else CVVAE_EINVAL).  gv == gy is allowed.  The GroupNorm part of the backward
+ * is cvvae_gn_bwd_input / cvvae_gn_bwd_input_params with silu = 0 on gv.
+ */
+int cvvae_gn_leaky_apply(int32_t dtype, const void* x, const float* scale, const float* shift, void* y, int64_t rows, int64_t per_row,
+                         int32_t C, float slope, void* stream);
+int cvvae_leaky_bwd(int32_t dtype, const void* y, const void* gy, void* gv, int64_t n_elems, float slope, void* stream);
 
 int cvvae_abi_version(void);
 /* name of the kernel instance cvvae_conv_fwd would launch for d (for profiling reports); NULL if unsupported */
