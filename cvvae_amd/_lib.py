@@ -119,6 +119,9 @@ PROTOTYPES = {
     "cvvae_avgpool3d_down_bwd": (_i32, [_i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "cvvae_gn_leaky_apply": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _f32, _vp]),
     "cvvae_leaky_bwd": (_i32, [_i32, _vp, _vp, _vp, _i64, _f32, _vp]),
+    "cvvae_pass_gn_slabs": (_i64, [_i64, _i64, _i32, _i32]),
+    "cvvae_avgpool3d_down_stats": (_i32, [_i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "cvvae_gn_leaky_apply_stats": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _f32, _i32, _vp, _vp]),
 }
 
 _lib = None

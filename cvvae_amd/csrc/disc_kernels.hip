@@ -1,7 +1,8 @@
 // disc_kernels.hip -- the non-convolution passes of the 3-D PatchGAN discriminator (cvvae_amd/disc_ops.py) and their adjoints:
 // ResnetBlockDown3D's downsample (first frame duplicated when T is odd, then avg_pool3d(2, 2)) and GroupNorm-apply + LeakyReLU
 // (or the bare LeakyReLU).  gfx950 only.  All four are HBM- or latency-bound element-wise passes over NDHWC tensors: plain C++,
-// fp32 arithmetic, one rounding to the storage dtype, no LDS, no atomics.
+// fp32 arithmetic, one rounding to the storage dtype, no atomics.  The two *_stats forms (further down) are the same passes that also
+// leave the GroupNorm records of the tensor they store; only they use LDS.
 //
 // Work split.  A lane owns one group of 8 consecutive channels (one 16-byte access for 16-bit types, two for fp32; C % 8 == 0 and
 // 16-byte aligned tensors make every group aligned), consecutive lanes take consecutive groups, so a wavefront covers whole lines
@@ -68,31 +69,40 @@ __device__ __forceinline__ Pos decode(long long g, int cv, int Hd, int Wd) {
 // models/discriminator.py:240-243, 250-253:  if T is odd, h = cat([h[:, :, :1], h], 2);  h = avg_pool3d(h, 2, 2).
 // Padded frame p is stored frame p (T even) or max(p - 1, 0) (T odd): the duplicate is an index rule, never a tensor.
 // ---------------------------------------------------------------------------------------------------------
+// one pooled 8-channel vector: the 8 inputs of output (b, to, oy, ox), summed pairwise in fp32 and scaled by 0.125.  Shared by the plain and
+// the statistics kernel, so both round the same fp32 value.
+template <typename T>
+__device__ __forceinline__ void pool8(const T* __restrict__ x, long long b, int to, int oy, int ox, int c0, int Tn, int H, int W, int C,
+                                      float (&r)[VEC]) {
+  const int odd = Tn & 1;
+  float s[2][VEC];  // one partial sum per padded frame: ((x00 + x01) + (x10 + x11))
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt) {
+    const int p = 2 * to + dt;
+    const int t = odd ? (p > 0 ? p - 1 : 0) : p;
+    const T* row0 = x + ((((b * Tn + t) * H + 2 * oy) * W + 2 * ox) * (long long)C + c0);
+    float a[VEC], c[VEC], d[VEC], e[VEC];
+    load8<T>(row0, a);
+    load8<T>(row0 + C, c);
+    load8<T>(row0 + (long long)W * C, d);
+    load8<T>(row0 + (long long)W * C + C, e);
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) s[dt][j] = (a[j] + c[j]) + (d[j] + e[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) r[j] = (s[0][j] + s[1][j]) * 0.125f;
+}
+
 template <typename T>
 __global__ __launch_bounds__(WG) void avgpool3d_down_kernel(const T* __restrict__ x, T* __restrict__ y, int Tn, int H, int W, int C,
                                                             int To, int Ho, int Wo, long long ngroups) {
-  const int cv = C / VEC, odd = Tn & 1;
+  const int cv = C / VEC;
   for (long long g = (long long)blockIdx.x * WG + threadIdx.x; g < ngroups; g += (long long)gridDim.x * WG) {
     const Pos o = decode(g, cv, Ho, Wo);
     const long long b = o.frame / To;
     const int to = (int)(o.frame - b * To);
-    float s[2][VEC];  // one partial sum per padded frame: ((x00 + x01) + (x10 + x11))
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt) {
-      const int p = 2 * to + dt;
-      const int t = odd ? (p > 0 ? p - 1 : 0) : p;
-      const T* row0 = x + ((((b * Tn + t) * H + 2 * o.y) * W + 2 * o.x) * (long long)C + o.c0);
-      float a[VEC], c[VEC], d[VEC], e[VEC];
-      load8<T>(row0, a);
-      load8<T>(row0 + C, c);
-      load8<T>(row0 + (long long)W * C, d);
-      load8<T>(row0 + (long long)W * C + C, e);
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) s[dt][j] = (a[j] + c[j]) + (d[j] + e[j]);
-    }
     float r[VEC];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) r[j] = (s[0][j] + s[1][j]) * 0.125f;
+    pool8<T>(x, b, to, o.y, o.x, o.c0, Tn, H, W, C, r);
     store8<T>(y + g * VEC, r);
   }
 }
@@ -127,6 +137,16 @@ __global__ __launch_bounds__(WG) void avgpool3d_down_bwd_kernel(const T* __restr
 // (scale, shift) tables of cvvae_gn_stats / cvvae_gn_finalize;  AFFINE = false: the bare LeakyReLU behind the first conv (:302).
 // x and y may alias.
 // ---------------------------------------------------------------------------------------------------------
+template <bool AFFINE>
+__device__ __forceinline__ void affine_leaky8(float (&f)[VEC], const float (&sc)[VEC], const float (&sh)[VEC], float slope) {
+  if constexpr (AFFINE) {
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) f[j] = __builtin_fmaf(f[j], sc[j], sh[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) f[j] = f[j] > 0.f ? f[j] : slope * f[j];
+}
+
 template <typename T, bool AFFINE>
 __global__ __launch_bounds__(WG) void gn_leaky_apply_kernel(const T* x, const float* __restrict__ scale, const float* __restrict__ shift,
                                                             T* y, long long per_row, int C, float slope, long long ngroups) {
@@ -134,17 +154,14 @@ __global__ __launch_bounds__(WG) void gn_leaky_apply_kernel(const T* x, const fl
   for (long long g = (long long)blockIdx.x * WG + threadIdx.x; g < ngroups; g += (long long)gridDim.x * WG) {
     float f[VEC];
     load8<T>(x + g * VEC, f);
+    float sc[VEC], sh[VEC];
     if constexpr (AFFINE) {
       const long long pix = g / cv;
       const long long tab = (pix / per_row) * C + (g - pix * cv) * VEC;
-      float sc[VEC], sh[VEC];
       load8<float>(scale + tab, sc);
       load8<float>(shift + tab, sh);
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) f[j] = __builtin_fmaf(f[j], sc[j], sh[j]);
     }
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) f[j] = f[j] > 0.f ? f[j] : slope * f[j];
+    affine_leaky8<AFFINE>(f, sc, sh, slope);
     store8<T>(y + g * VEC, f);
   }
 }
@@ -173,6 +190,151 @@ __global__ __launch_bounds__(WG) void leaky_bwd_kernel(const T* y, const T* gy, 
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The same two passes with the GroupNorm records of the tensor they STORE (cvvae_gn_leaky_apply_stats, cvvae_avgpool3d_down_stats):
+// part[row][group][slab] = (n, mean, M2) of the rounded values, the format cvvae_gn_finalize merges.  Grid (slabs, rows): a workgroup
+// owns one contiguous run of one row's pixels, so it never straddles two samples and writes exactly one record per group; no atomics.
+// Thread tid = pixel lane * cv + channel vector (cv = C / 8, ppp = WG / cv pixel lanes; threads beyond cv * ppp idle), as in
+// gn_partial_kernel: a thread keeps its channel vector for the whole run, hence its statistics slots and, for the affine form, its
+// eight table entries.
+//
+// A lane's 8 channels are 8 / SUB statistics slots of SUB channels: SUB = 2 for groups of 2 or 6 channels (Normalize(64): the lane holds
+// four groups), 4 for groups of 4, 12, ... (two), 8 when a group is whole lanes (one slot; a 16-channel group is two lanes).  All slots
+// of a lane have seen the same number of pixels k, so one Chan / Welford step per pixel serves them all:  f = 1 / (k + 1),
+// mean += (m - mean) f,  M2 += m2 + (m - mean)^2 SUB k f,  (m, m2) the exact two-pass statistics of the SUB new values.
+// The slots meet in LDS; group g's thread merges them in a fixed order (pixel lane, then slot): the same inputs give the same bits.
+// ---------------------------------------------------------------------------------------------------------
+struct WStat {
+  float n, mean, m2;
+};
+__device__ __forceinline__ void chan_merge(WStat& a, const WStat& b) {
+  if (b.n == 0.f) return;
+  const float n = a.n + b.n;
+  const float d = b.mean - a.mean;
+  const float f = b.n / n;
+  a.mean += d * f;
+  a.m2 += b.m2 + d * d * a.n * f;
+  a.n = n;
+}
+
+// the value the store leaves in memory
+template <typename T>
+__device__ __forceinline__ void round8(float (&f)[VEC]) {
+  if constexpr (sizeof(T) != 4) {
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) f[j] = (float)(T)f[j];
+  }
+}
+
+template <int SUB>
+struct LaneStats {
+  static constexpr int NS = VEC / SUB;
+  float mean[NS], m2[NS], k;
+  __device__ __forceinline__ void init() {
+#pragma unroll
+    for (int h = 0; h < NS; ++h) mean[h] = m2[h] = 0.f;
+    k = 0.f;
+  }
+  __device__ __forceinline__ void add(const float (&f)[VEC]) {
+    const float fk = 1.f / (k + 1.f), w = (float)SUB * k * fk;
+#pragma unroll
+    for (int h = 0; h < NS; ++h) {
+      float sum = 0.f;
+      if constexpr (SUB == 2) sum = f[h * 2] + f[h * 2 + 1];
+      if constexpr (SUB == 4) sum = (f[h * 4] + f[h * 4 + 1]) + (f[h * 4 + 2] + f[h * 4 + 3]);
+      if constexpr (SUB == 8) sum = ((f[0] + f[1]) + (f[2] + f[3])) + ((f[4] + f[5]) + (f[6] + f[7]));
+      const float mb = sum * (1.0f / SUB);
+      float m2b = 0.f;
+#pragma unroll
+      for (int j = 0; j < SUB; ++j) {
+        const float d = f[h * SUB + j] - mb;
+        m2b += d * d;
+      }
+      const float d = mb - mean[h];
+      mean[h] += d * fk;
+      m2[h] += m2b + d * d * w;
+    }
+    k += 1.f;
+  }
+};
+
+// every thread of the workgroup calls this once, after its run: one record per group to rec[g * rec_stride]
+template <int SUB>
+__device__ __forceinline__ void write_group_records(const LaneStats<SUB>& st, int cv, int ppp, int G, int C, float* rec, long long rec_stride) {
+  constexpr int NS = VEC / SUB;
+  __shared__ WStat sh[WG * NS];
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int h = 0; h < NS; ++h) sh[tid * NS + h] = {(float)SUB * st.k, st.mean[h], st.m2[h]};  // k = 0 (idle thread, empty run): merged as nothing
+  __syncthreads();
+  for (int g = tid; g < G; g += WG) {
+    const int spg = C / G / SUB;  // slots per group
+    WStat acc = {0.f, 0.f, 0.f};
+    for (int pl = 0; pl < ppp; ++pl)
+      for (int q = g * spg; q < (g + 1) * spg; ++q) chan_merge(acc, sh[(pl * cv + q / NS) * NS + q % NS]);
+    float* o = rec + (long long)g * rec_stride;
+    o[0] = acc.n;
+    o[1] = acc.mean;
+    o[2] = acc.m2;
+  }
+}
+
+template <typename T, bool AFFINE, int SUB>
+__global__ __launch_bounds__(WG) void gn_leaky_apply_stats_kernel(const T* x, const float* __restrict__ scale,
+                                                                  const float* __restrict__ shift, T* y, long long per_row, int C,
+                                                                  float slope, int G, float* __restrict__ part) {
+  const int slabs = gridDim.x, slab = blockIdx.x, row = blockIdx.y;
+  const int cv = C / VEC, ppp = WG / cv;
+  const int myv = threadIdx.x % cv, mypl = threadIdx.x / cv;
+  const long long per = (per_row + slabs - 1) / slabs, p0 = slab * per;
+  const long long p1 = p0 + per < per_row ? p0 + per : per_row;
+  LaneStats<SUB> st;
+  st.init();
+  if (mypl < ppp) {
+    float sc[VEC], sh[VEC];
+    if constexpr (AFFINE) {
+      load8<float>(scale + (long long)row * C + myv * VEC, sc);
+      load8<float>(shift + (long long)row * C + myv * VEC, sh);
+    }
+    const long long base = (long long)row * per_row * C + myv * VEC;
+    for (long long px = p0 + mypl; px < p1; px += ppp) {
+      float f[VEC];
+      load8<T>(x + base + px * C, f);
+      affine_leaky8<AFFINE>(f, sc, sh, slope);
+      round8<T>(f);
+      store8<T>(y + base + px * C, f);
+      st.add(f);
+    }
+  }
+  write_group_records<SUB>(st, cv, ppp, G, C, part + ((long long)row * G * slabs + slab) * 3, (long long)slabs * 3);
+}
+
+template <typename T, int SUB>
+__global__ __launch_bounds__(WG) void avgpool3d_down_stats_kernel(const T* __restrict__ x, T* __restrict__ y, int Tn, int H, int W, int C,
+                                                                  int To, int Ho, int Wo, int G, float* __restrict__ part) {
+  const int slabs = gridDim.x, slab = blockIdx.x, row = blockIdx.y;
+  const int cv = C / VEC, ppp = WG / cv;
+  const int myv = threadIdx.x % cv, mypl = threadIdx.x / cv;
+  const long long frame_pix = (long long)Ho * Wo, per_row = frame_pix * To;
+  const long long per = (per_row + slabs - 1) / slabs, p0 = slab * per;
+  const long long p1 = p0 + per < per_row ? p0 + per : per_row;
+  LaneStats<SUB> st;
+  st.init();
+  if (mypl < ppp) {
+    for (long long px = p0 + mypl; px < p1; px += ppp) {
+      const int to = (int)(px / frame_pix);
+      const unsigned r = (unsigned)(px - to * frame_pix);
+      const int oy = (int)(r / (unsigned)Wo), ox = (int)(r - (unsigned)oy * (unsigned)Wo);
+      float f[VEC];
+      pool8<T>(x, row, to, oy, ox, myv * VEC, Tn, H, W, C, f);
+      round8<T>(f);
+      store8<T>(y + ((long long)row * per_row + px) * C + myv * VEC, f);
+      st.add(f);
+    }
+  }
+  write_group_records<SUB>(st, cv, ppp, G, C, part + ((long long)row * G * slabs + slab) * 3, (long long)slabs * 3);
+}
+
 static inline int blocks_for(long long ngroups) {
   const long long b = (ngroups + WG - 1) / WG;
   return (int)(b < MAX_BLOCKS ? b : MAX_BLOCKS);
@@ -189,6 +351,19 @@ static inline long long pool_elems(int64_t B, int32_t T, int32_t H, int32_t W, i
   if (pix > MAX_ELEMS / C) return -1;
   return pix * C;
 }
+
+constexpr int MAX_STAT_C = WG * VEC;  // one thread per channel vector at least
+constexpr int MAX_STAT_ROWS = 65535;  // gridDim.y
+
+// 0, or why the statistics forms cannot take (rows, per_row, C, groups)
+static inline int stats_args(int64_t rows, int64_t per_row, int32_t C, int32_t groups) {
+  if (rows <= 0 || per_row <= 0 || C <= 0 || groups <= 0) return CVVAE_EINVAL;
+  if (C % VEC || C > MAX_STAT_C || C % groups || (C / groups) % 2 || groups > WG || rows > MAX_STAT_ROWS) return CVVAE_EUNSUPPORTED;
+  return 0;
+}
+
+// channels per statistics slot for groups of cpg channels (cpg even)
+static inline int sub_for(int cpg) { return cpg % 8 == 0 ? 8 : cpg % 4 == 0 ? 4 : 2; }
 
 }  // namespace disc
 }  // namespace cvvae
@@ -261,6 +436,67 @@ int cvvae_leaky_bwd(int32_t dtype, const void* y, const void* gy, void* gv, int6
                      (TT*)gv, (long long)n_elems, slope)
   DISC_BY_DTYPE(CALL);
 #undef CALL
+  return (int)hipGetLastError();
+}
+
+int64_t cvvae_pass_gn_slabs(int64_t rows, int64_t per_row, int32_t C, int32_t groups) {
+  const int bad = stats_args(rows, per_row, C, groups);
+  if (bad) return bad;
+  // a workgroup's run: at least 16 trips of its WG / (C / 8) pixel lanes, and about MAX_BLOCKS workgroups in all at most
+  const int64_t run = 16 * (WG / (C / VEC));
+  const int64_t want = (per_row + run - 1) / run, cap = MAX_BLOCKS / rows > 0 ? MAX_BLOCKS / rows : 1;
+  return want < cap ? want : cap;
+}
+
+#define DISC_BY_SUB(CALL, TT) \
+  do { \
+    if (sub == 8) { CALL(TT, 8); } else if (sub == 4) { CALL(TT, 4); } else { CALL(TT, 2); } \
+  } while (0)
+
+int cvvae_avgpool3d_down_stats(int32_t dtype, const void* x, void* y, int64_t B, int32_t T, int32_t H, int32_t W, int32_t C,
+                               int32_t out_groups, float* out_partials, void* stream) {
+  if (out_groups < 0) return CVVAE_EINVAL;
+  if (out_groups == 0 || !out_partials) return cvvae_avgpool3d_down(dtype, x, y, B, T, H, W, C, stream);
+  if (!x || !y || B <= 0 || T <= 0 || H < 2 || W < 2 || C <= 0) return CVVAE_EINVAL;
+  if (!known_dtype(dtype) || C % VEC) return CVVAE_EUNSUPPORTED;
+  if (pool_elems(B, T, H, W, C) < 0) return CVVAE_EUNSUPPORTED;
+  const int To = (T + (T & 1)) / 2, Ho = H / 2, Wo = W / 2;
+  const int64_t slabs = cvvae_pass_gn_slabs(B, (int64_t)To * Ho * Wo, C, out_groups);
+  if (slabs <= 0) return (int)slabs;
+  const int sub = sub_for(C / out_groups);
+#define CALL_S(TT, SUB) \
+  hipLaunchKernelGGL((avgpool3d_down_stats_kernel<TT, SUB>), dim3((unsigned)slabs, (unsigned)B), dim3(WG), 0, (hipStream_t)stream, \
+                     (const TT*)x, (TT*)y, T, H, W, C, To, Ho, Wo, out_groups, out_partials)
+#define CALL(TT) DISC_BY_SUB(CALL_S, TT)
+  DISC_BY_DTYPE(CALL);
+#undef CALL
+#undef CALL_S
+  return (int)hipGetLastError();
+}
+
+int cvvae_gn_leaky_apply_stats(int32_t dtype, const void* x, const float* scale, const float* shift, void* y, int64_t rows,
+                               int64_t per_row, int32_t C, float slope, int32_t out_groups, float* out_partials, void* stream) {
+  if (out_groups < 0) return CVVAE_EINVAL;
+  if (out_groups == 0 || !out_partials) return cvvae_gn_leaky_apply(dtype, x, scale, shift, y, rows, per_row, C, slope, stream);
+  if (!x || !y || rows <= 0 || per_row <= 0 || C <= 0 || (scale == nullptr) != (shift == nullptr)) return CVVAE_EINVAL;
+  if (!known_dtype(dtype) || C % VEC) return CVVAE_EUNSUPPORTED;
+  if (rows > MAX_ELEMS / per_row || rows * per_row > MAX_ELEMS / C) return CVVAE_EUNSUPPORTED;
+  const int64_t slabs = cvvae_pass_gn_slabs(rows, per_row, C, out_groups);
+  if (slabs <= 0) return (int)slabs;
+  const int sub = sub_for(C / out_groups);
+#define CALL_S(TT, SUB) \
+  do { \
+    if (scale) \
+      hipLaunchKernelGGL((gn_leaky_apply_stats_kernel<TT, true, SUB>), dim3((unsigned)slabs, (unsigned)rows), dim3(WG), 0, \
+                         (hipStream_t)stream, (const TT*)x, scale, shift, (TT*)y, (long long)per_row, C, slope, out_groups, out_partials); \
+    else \
+      hipLaunchKernelGGL((gn_leaky_apply_stats_kernel<TT, false, SUB>), dim3((unsigned)slabs, (unsigned)rows), dim3(WG), 0, \
+                         (hipStream_t)stream, (const TT*)x, scale, shift, (TT*)y, (long long)per_row, C, slope, out_groups, out_partials); \
+  } while (0)
+#define CALL(TT) DISC_BY_SUB(CALL_S, TT)
+  DISC_BY_DTYPE(CALL);
+#undef CALL
+#undef CALL_S
   return (int)hipGetLastError();
 }
 

@@ -1136,13 +1136,30 @@ def avgpool3d_down_shape(shape) -> Tuple[int, int, int, int, int]:
     return (B, (T + (T & 1)) // 2, H // 2, W // 2, C)
 
 
-def avgpool3d_down(x: torch.Tensor) -> torch.Tensor:
+def _pass_partials(lib, rows: int, per_row: int, C: int, groups: int, device) -> GNPartials:
+    """the record buffer of a *_stats pass over a [rows, per_row, C] tensor (cvvae_pass_gn_slabs)"""
+    slabs = int(lib.cvvae_pass_gn_slabs(rows, per_row, C, groups))
+    if slabs <= 0:
+        L.check(slabs, "cvvae_pass_gn_slabs")
+    return GNPartials(torch.empty((rows, groups, slabs, 3), dtype=torch.float32, device=device), rows, slabs, C, groups)
+
+
+def avgpool3d_down(x: torch.Tensor, gn_out: int = 0):
     """ResnetBlockDown3D's downsample on x [B,T,H,W,C] (cvvae_avgpool3d_down): an odd T gets its first frame duplicated in front
-    (never materialised), then avg_pool3d(2, 2): [B, ceil(T/2), H//2, W//2, C]"""
+    (never materialised), then avg_pool3d(2, 2): [B, ceil(T/2), H//2, W//2, C].
+    gn_out = G > 0 (cvvae_avgpool3d_down_stats): also returns the GNPartials of the pooled tensor for a following G-group GroupNorm
+    (gn_finalize); the tensor has the same bits."""
     lib = L.load()
     _ndhwc(x, "avgpool3d_down")
     B, T, H, W, C = x.shape
-    out = torch.empty(avgpool3d_down_shape(x.shape), dtype=x.dtype, device=x.device)
+    oshape = avgpool3d_down_shape(x.shape)
+    if gn_out:
+        part = _pass_partials(lib, B, oshape[1] * oshape[2] * oshape[3], C, gn_out, x.device)
+        out = torch.empty(oshape, dtype=x.dtype, device=x.device)
+        L.check(lib.cvvae_avgpool3d_down_stats(_dt(x.dtype), x.data_ptr(), out.data_ptr(), B, T, H, W, C, gn_out, part.buf.data_ptr(),
+                                               _stream(x)), "cvvae_avgpool3d_down_stats")
+        return out, part
+    out = torch.empty(oshape, dtype=x.dtype, device=x.device)
     L.check(lib.cvvae_avgpool3d_down(_dt(x.dtype), x.data_ptr(), out.data_ptr(), B, T, H, W, C, _stream(x)), "cvvae_avgpool3d_down")
     return out
 
@@ -1162,9 +1179,11 @@ def avgpool3d_down_bwd(gy: torch.Tensor, shape) -> torch.Tensor:
 
 
 def gn_leaky_apply(x: torch.Tensor, gn: Optional[Tuple[torch.Tensor, torch.Tensor]], slope: float = 0.2,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, gn_out: int = 0):
     """leaky_relu(x * scale + shift, slope) once per element (cvvae_gn_leaky_apply): x [B,T,H,W,C], gn = (scale, shift) fp32 tables
-    [B, C] of gn_stats / gn_finalize, or None for the bare LeakyReLU.  out = x runs in place."""
+    [B, C] of gn_stats / gn_finalize, or None for the bare LeakyReLU.  out = x runs in place.
+    gn_out = G > 0 (cvvae_gn_leaky_apply_stats): also returns the GNPartials of the stored result for a following G-group GroupNorm
+    (gn_finalize); the tensor has the same bits."""
     lib = L.load()
     _ndhwc(x, "gn_leaky_apply")
     B, T, H, W, C = x.shape
@@ -1178,6 +1197,12 @@ def gn_leaky_apply(x: torch.Tensor, gn: Optional[Tuple[torch.Tensor, torch.Tenso
         out = torch.empty_like(x)
     elif out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
         raise ValueError("gn_leaky_apply: out must be a contiguous tensor like x")
+    if gn_out:
+        part = _pass_partials(lib, B, T * H * W, C, gn_out, x.device)
+        L.check(lib.cvvae_gn_leaky_apply_stats(_dt(x.dtype), x.data_ptr(), sc.data_ptr() if sc is not None else None,
+                                               sh.data_ptr() if sh is not None else None, out.data_ptr(), B, T * H * W, C, slope, gn_out,
+                                               part.buf.data_ptr(), _stream(x)), "cvvae_gn_leaky_apply_stats")
+        return out, part
     L.check(lib.cvvae_gn_leaky_apply(_dt(x.dtype), x.data_ptr(), sc.data_ptr() if sc is not None else None,
                                      sh.data_ptr() if sh is not None else None, out.data_ptr(), B, T * H * W, C, slope, _stream(x)),
             "cvvae_gn_leaky_apply")

@@ -558,6 +558,24 @@ int cvvae_gn_leaky_apply(int32_t dtype, const void* x, const float* scale, const
                          int32_t C, float slope, void* stream);
 int cvvae_leaky_bwd(int32_t dtype, const void* y, const void* gy, void* gv, int64_t n_elems, float slope, void* stream);
 
+/*
+ * The two passes above with the GroupNorm records of the tensor they STORE, for producers of a GroupNorm input that are not convs
+ * (the LeakyReLU pass in front of a block's norm1, the pool in front of a downsampling block's norm2):
+ * out_partials: [rows][out_groups][slabs][3] fp32 records (n, mean, M2) of the ROUNDED stored values, the format of cvvae_conv_fwd_gn;
+ * slabs = cvvae_pass_gn_slabs(rows, per_row, C, out_groups) with per_row the pixels of one sample of the STORED tensor (for the pool:
+ * To Ho Wo, rows = B).  One workgroup per (slab, row): none straddles two samples, every record is written exactly once (an empty slab
+ * writes n = 0, which the merge skips), no atomics: results are bit-reproducible.  cvvae_gn_finalize merges them.  y has the bits of
+ * the plain entry point.  out_groups = 0 or out_partials = NULL: the plain pass; out_groups < 0: CVVAE_EINVAL.  With records:
+ * C <= 2048, out_groups <= 256 dividing C, an even number of channels per group (2, 4, 8, 16, ... of Normalize(64 ... 512) are all
+ * taken), rows <= 65535; else CVVAE_EUNSUPPORTED.
+ * cvvae_pass_gn_slabs is pure host code: > 0, or the CVVAE_E* code the launch would return for these extents.
+ */
+int64_t cvvae_pass_gn_slabs(int64_t rows, int64_t per_row, int32_t C, int32_t groups);
+int cvvae_avgpool3d_down_stats(int32_t dtype, const void* x, void* y, int64_t B, int32_t T, int32_t H, int32_t W, int32_t C,
+                               int32_t out_groups, float* out_partials, void* stream);
+int cvvae_gn_leaky_apply_stats(int32_t dtype, const void* x, const float* scale, const float* shift, void* y, int64_t rows,
+                               int64_t per_row, int32_t C, float slope, int32_t out_groups, float* out_partials, void* stream);
+
 int cvvae_abi_version(void);
 /* name of the kernel instance cvvae_conv_fwd would launch for d (for profiling reports); NULL if unsupported */
 const char* cvvae_conv_kernel_name(const cvvae_conv_desc* d);
