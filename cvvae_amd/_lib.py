@@ -122,6 +122,7 @@ PROTOTYPES = {
     "cvvae_pass_gn_slabs": (_i64, [_i64, _i64, _i32, _i32]),
     "cvvae_avgpool3d_down_stats": (_i32, [_i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "cvvae_gn_leaky_apply_stats": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _f32, _i32, _vp, _vp]),
+    "cvvae_conv333_s2_dgrad_small": (_i32, [_i32, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
 }
 
 _lib = None

@@ -335,6 +335,97 @@ __global__ __launch_bounds__(WG) void avgpool3d_down_stats_kernel(const T* __res
   write_group_records<SUB>(st, cv, ppp, G, C, part + ((long long)row * G * slabs + slab) * 3, (long long)slabs * 3);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Input gradient of a 3x3x3 conv with stride (2,2,2), zero padding 1 and Cin <= 8 (the discriminator's first layer, 3 -> 64), as a
+// GATHER over the output gradient:  gx[b,t,h,w,ci] = sum over (kt,kh,kw), co of gy[b,ot,oh,ow,co] W[co,ci,kt,kh,kw],  ot = (t + 1 - kt) / 2
+// where t + 1 - kt is even and 0 <= ot < To (oh, ow alike): an even coordinate has one live tap on its axis (k = 1), an odd one two
+// (k = 0 and k = 2), so an input pixel reads 1 .. 8 output pixels.  No zero-stuffed tensor, no MFMA tile padded from 3 to 32 columns.
+//
+// Work split.  A WAVE owns 64 column pairs of one input row (b, t, h): lane j of the chunk computes pixels w = 2j and 2j + 1 from the
+// output pixels ow = j (tap kw = 1 for the even pixel, kw = 2 for the odd one) and ow = j + 1 (kw = 0, odd pixel), so
+//   * the live (kt, kh) taps are the same for the whole wave (t, h are wave-uniform): no divergence, and the weight reads are
+//     same-address LDS broadcasts;
+//   * a lane stores its two pixels side by side (2 x 8 channels: 32 contiguous bytes in 16-bit types), consecutive lanes consecutive
+//     pairs: full lines;
+//   * gy is read in 16-byte vectors along C; neighbouring lanes share ow = j + 1 through the vector cache.
+// The weights sit in LDS as fp32 [27][Cout][CI], CI = 4 (Cin <= 4) or 8, staged once per workgroup from the caller's [27][Cout][8] table;
+// the grid is capped and the waves stride over the row chunks, so the staging is amortised.  fp32 FMAs in a fixed order (kt, kh, then
+// co ascending; per co the kw = 0 product before the kw = 2 one), one rounding at the store, every element one writer: the same inputs
+// give the same bits.  Channels >= Cin of the 8-channel result are written as zero.  Row-chunk and element indices are 64-bit.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int DG_WAVES = WG / 64;
+constexpr int DG_MAX_BLOCKS = 1024;
+constexpr int DG_MAX_LDS = 64 * 1024;
+
+template <typename T, int CI>
+__global__ __launch_bounds__(WG) void conv333_s2_dgrad_small_kernel(const T* __restrict__ gy, long long gy_stride,
+                                                                    const float* __restrict__ wtab, T* __restrict__ gx, int Tn, int H,
+                                                                    int W, int To, int Ho, int Wo, int Cout, int nchunk,
+                                                                    long long nunits) {
+  extern __shared__ __attribute__((aligned(16))) float dg_w[];  // [27][Cout][CI]
+  for (int i = threadIdx.x; i < 27 * Cout * CI; i += WG) dg_w[i] = wtab[(long long)(i / CI) * VEC + (i % CI)];
+  __syncthreads();
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const int npairs = (W + 1) >> 1;
+  for (long long u = (long long)blockIdx.x * DG_WAVES + wave; u < nunits; u += (long long)gridDim.x * DG_WAVES) {
+    const long long row = u / nchunk;                      // (b, t, h) flattened
+    const int j = (int)(u - row * nchunk) * 64 + lane;     // column pair
+    const long long bt = row / H;
+    const int h = (int)(row - bt * H);
+    const long long b = bt / Tn;
+    const int t = (int)(bt - b * Tn);
+    const bool has_a = j < npairs, has_b = j + 1 < Wo;     // (j < npairs implies j < Wo)
+    float acc0[CI], acc1[CI];
+#pragma unroll
+    for (int c = 0; c < CI; ++c) acc0[c] = acc1[c] = 0.f;
+    for (int kt = 0; kt < 3; ++kt) {
+      const int nt = t + 1 - kt;
+      if (nt < 0 || (nt & 1) || (nt >> 1) >= To) continue;
+      for (int kh = 0; kh < 3; ++kh) {
+        const int nh = h + 1 - kh;
+        if (nh < 0 || (nh & 1) || (nh >> 1) >= Ho) continue;
+        if (!has_a) continue;
+        const T* pa = gy + ((((b * To + (nt >> 1)) * Ho + (nh >> 1)) * (long long)Wo + j) * gy_stride);
+        const float* w0 = dg_w + (kt * 9 + kh * 3) * Cout * CI;  // taps kw = 0, 1, 2 follow each other
+        const float* w1 = w0 + Cout * CI;
+        const float* w2 = w1 + Cout * CI;
+        for (int c8 = 0; c8 < Cout; c8 += VEC) {
+          float a[VEC], bb[VEC];
+          load8<T>(pa + c8, a);
+          if (has_b) {
+            load8<T>(pa + gy_stride + c8, bb);
+          } else {
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) bb[q] = 0.f;
+          }
+#pragma unroll
+          for (int q = 0; q < VEC; ++q) {
+            const int o = (c8 + q) * CI;
+#pragma unroll
+            for (int c = 0; c < CI; ++c) {
+              acc0[c] = __builtin_fmaf(a[q], w1[o + c], acc0[c]);
+              acc1[c] = __builtin_fmaf(bb[q], w0[o + c], acc1[c]);
+              acc1[c] = __builtin_fmaf(a[q], w2[o + c], acc1[c]);
+            }
+          }
+        }
+      }
+    }
+    if (has_a) {
+      float r[VEC];
+#pragma unroll
+      for (int c = 0; c < VEC; ++c) r[c] = c < CI ? acc0[c < CI ? c : 0] : 0.f;
+      T* po = gx + ((row * W + 2 * (long long)j) * VEC);
+      store8<T>(po, r);
+      if (2 * j + 1 < W) {
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) r[c] = c < CI ? acc1[c < CI ? c : 0] : 0.f;
+        store8<T>(po + VEC, r);
+      }
+    }
+  }
+}
+
 static inline int blocks_for(long long ngroups) {
   const long long b = (ngroups + WG - 1) / WG;
   return (int)(b < MAX_BLOCKS ? b : MAX_BLOCKS);
@@ -497,6 +588,35 @@ int cvvae_gn_leaky_apply_stats(int32_t dtype, const void* x, const float* scale,
   DISC_BY_DTYPE(CALL);
 #undef CALL
 #undef CALL_S
+  return (int)hipGetLastError();
+}
+
+int cvvae_conv333_s2_dgrad_small(int32_t dtype, const void* gy, int64_t gy_pix_stride, const float* w_table, void* gx, int64_t B,
+                                 int32_t T, int32_t H, int32_t W, int32_t To, int32_t Ho, int32_t Wo, int32_t Cin, int32_t Cout,
+                                 void* stream) {
+  if (!gy || !w_table || !gx || B <= 0 || T <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || gy_pix_stride <= 0) return CVVAE_EINVAL;
+  // the forward's output extents, from the input's: floor((n + 2 - 3) / 2) + 1
+  if (To != (T - 1) / 2 + 1 || Ho != (H - 1) / 2 + 1 || Wo != (W - 1) / 2 + 1) return CVVAE_EINVAL;
+  if (!known_dtype(dtype) || Cin > VEC || Cout % VEC || gy_pix_stride % VEC || gy_pix_stride < Cout) return CVVAE_EUNSUPPORTED;
+  if (((uintptr_t)gy | (uintptr_t)gx | (uintptr_t)w_table) & 15) return CVVAE_EUNSUPPORTED;
+  const int ci = Cin <= 4 ? 4 : 8;
+  const long long lds = 27LL * Cout * ci * (long long)sizeof(float);
+  if (lds > DG_MAX_LDS) return CVVAE_EUNSUPPORTED;
+  if (pool_elems(B, T, H, W, VEC) < 0 || (long long)B * To * Ho * Wo > MAX_ELEMS / gy_pix_stride) return CVVAE_EUNSUPPORTED;
+  const int nchunk = (((W + 1) >> 1) + 63) / 64;
+  const long long nunits = (long long)B * T * H * nchunk;
+  const long long want = (nunits + DG_WAVES - 1) / DG_WAVES;
+  const int blocks = (int)(want < DG_MAX_BLOCKS ? want : DG_MAX_BLOCKS);
+#define CALL_C(TT, CC) \
+  hipLaunchKernelGGL((conv333_s2_dgrad_small_kernel<TT, CC>), dim3(blocks), dim3(WG), (size_t)lds, (hipStream_t)stream, (const TT*)gy, \
+                     (long long)gy_pix_stride, w_table, (TT*)gx, T, H, W, To, Ho, Wo, Cout, nchunk, nunits)
+#define CALL(TT) \
+  do { \
+    if (ci == 4) { CALL_C(TT, 4); } else { CALL_C(TT, 8); } \
+  } while (0)
+  DISC_BY_DTYPE(CALL);
+#undef CALL
+#undef CALL_C
   return (int)hipGetLastError();
 }
 

@@ -359,6 +359,16 @@ class WeightCache:
         self._c[tag] = (key, out)
         return out
 
+    def cached(self, tag: str, names: Tuple[str, ...], make):
+        """a derived form of the parameters `names` that is none of the above (e.g. another module's repacked table): make(*params)
+        is called when the entry is missing or its source parameters have moved on, exactly as for every packed weight here"""
+        ps = [self.p(n) for n in names]
+        key = self._key(*ps)
+        hit = self._c.get(tag)
+        if hit is None or hit[0] != key:
+            hit = self._c[tag] = (key, make(*ps), tuple(names))
+        return hit[1]
+
     def norm(self, pre: str) -> Tuple[torch.Tensor, torch.Tensor]:
         g = self.p(pre + ".weight")
         b = self.p(pre + ".bias")

@@ -19,8 +19,8 @@ The reference's `rec_loss = |x - xhat| + perceptual_weight * p_loss` broadcasts 
 so no full-size temporary exists.  What combines 0-dim tensors (these formulas, exp of the logvar, the clamp of the adaptive
 weight) stays in torch and its autograd: the cotangent a `reduce` node receives IS gout / (exp(logvar) N), read by the adjoint
 kernel from device memory, and the gradients of the logvars and of p_loss are torch's scalar expressions of the saved sums.
-torch also keeps: the random numbers of the posterior sample, the discriminator (an arbitrary nn.Module: no discriminator network
-ships yet), and the `b c t h w -> (b t) c h w` copy that hands LPIPS its per-frame tensors.
+torch also keeps: the random numbers of the posterior sample, the discriminator (an arbitrary nn.Module; the training config's 3-D PatchGAN is
+cvvae_amd/discriminator.py, one autograd node on the same library), and the `b c t h w -> (b t) c h w` copy that hands LPIPS its per-frame tensors.
 
 Sums are fp32 whatever the operands' dtypes (fp16 / bf16 / fp32, mixed freely), so the loss, the logs and `kl_loss` are fp32
 0-dim tensors.  There is no eager fallback: CPU tensors raise.  Not built: `log_images`, `scale_input_to_tgt_size=True`,

@@ -1222,3 +1222,45 @@ def leaky_bwd(y: torch.Tensor, gy: torch.Tensor, slope: float = 0.2, out: Option
     L.check(lib.cvvae_leaky_bwd(_dt(y.dtype), y.data_ptr(), gy.data_ptr(), out.data_ptr(), y.numel(), slope, _stream(y)),
             "cvvae_leaky_bwd")
     return out
+
+
+def dgrad_small_table(w: torch.Tensor) -> torch.Tensor:
+    """a [Cout, Cin <= 8, 3, 3, 3] conv weight as the fp32 [27, Cout, 8] table of cvvae_conv333_s2_dgrad_small:
+    entry [(kt*3+kh)*3+kw, co, ci] = w[co, ci, kt, kh, kw], zero for ci >= Cin (an exact conversion for every storage dtype)"""
+    if w.dim() != 5 or tuple(w.shape[2:]) != (3, 3, 3) or w.shape[1] > 8:
+        raise NotImplementedError(f"conv333_s2_dgrad_small: a [Cout, Cin <= 8, 3, 3, 3] weight is required; got {tuple(w.shape)}")
+    co, ci = w.shape[0], w.shape[1]
+    tab = torch.zeros((27, co, 8), dtype=torch.float32, device=w.device)
+    tab[:, :, :ci] = w.detach().to(torch.float32).permute(2, 3, 4, 0, 1).reshape(27, co, ci)
+    return tab
+
+
+def conv333_s2_dgrad_small(gy: torch.Tensor, w: torch.Tensor, in_shape, cin: int) -> torch.Tensor:
+    """Input gradient of conv3d(x, w, stride 2, zero padding 1) with cin <= 8 input channels as a direct gather
+    (cvvae_conv333_s2_dgrad_small): gy [B,To,Ho,Wo,Cg] (Cg >= Cout, channels >= Cout never read), w the layer's own
+    [Cout, cin, 3, 3, 3] weight (or its dgrad_small_table), in_shape = (B, T, H, W) of the forward's input -> [B,T,H,W,8] in gy's
+    dtype, channels >= cin zero.  Every limit is checked here, before the launch."""
+    lib = L.load()
+    _need_gpu(gy)
+    B, T, H, W = (int(s) for s in in_shape)
+    tab = w if (w.dim() == 3 and w.dtype == torch.float32) else dgrad_small_table(w)
+    if tab.dim() != 3 or tab.shape[0] != 27 or tab.shape[2] != 8 or not tab.is_contiguous() or tab.device != gy.device:
+        raise ValueError(f"conv333_s2_dgrad_small: the weight table must be a contiguous fp32 [27, Cout, 8] tensor on {gy.device}")
+    cout = int(tab.shape[1])
+    if w.dim() == 5 and int(w.shape[1]) != int(cin):
+        raise ValueError(f"conv333_s2_dgrad_small: cin = {cin} but the weight has {w.shape[1]} input channels")
+    if not 1 <= cin <= 8:
+        raise NotImplementedError(f"conv333_s2_dgrad_small: Cin <= 8 is what the kernel takes (got {cin}); wider layers: grad3d.dgrad333")
+    if cout % 8:
+        raise NotImplementedError(f"conv333_s2_dgrad_small: Cout must be a multiple of 8 (got {cout})")
+    if 27 * cout * (4 if cin <= 4 else 8) * 4 > 65536:
+        raise NotImplementedError(f"conv333_s2_dgrad_small: the weight table of Cout = {cout}, Cin = {cin} does not fit 64 KiB of LDS")
+    oshape = (B, (T - 1) // 2 + 1, (H - 1) // 2 + 1, (W - 1) // 2 + 1)
+    if gy.dim() != 5 or not gy.is_contiguous() or tuple(gy.shape[:4]) != oshape or gy.shape[-1] < cout or gy.shape[-1] % 8:
+        raise ValueError(f"conv333_s2_dgrad_small: gy must be a contiguous [{', '.join(map(str, oshape))}, >= {cout} (a multiple of 8)] "
+                         f"tensor for an input of {(B, T, H, W)}; got {tuple(gy.shape)}")
+    out = torch.empty((B, T, H, W, 8), dtype=gy.dtype, device=gy.device)
+    L.check(lib.cvvae_conv333_s2_dgrad_small(_dt(gy.dtype), gy.data_ptr(), gy.shape[-1], tab.data_ptr(), out.data_ptr(), B, T, H, W,
+                                             oshape[1], oshape[2], oshape[3], int(cin), cout, _stream(gy)),
+            "cvvae_conv333_s2_dgrad_small")
+    return out

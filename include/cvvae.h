@@ -576,6 +576,22 @@ int cvvae_avgpool3d_down_stats(int32_t dtype, const void* x, void* y, int64_t B,
 int cvvae_gn_leaky_apply_stats(int32_t dtype, const void* x, const float* scale, const float* shift, void* y, int64_t rows,
                                int64_t per_row, int32_t C, float slope, int32_t out_groups, float* out_partials, void* stream);
 
+/*
+ * cvvae_conv333_s2_dgrad_small: the input gradient of a 3x3x3 conv with stride (2,2,2), zero padding 1 and Cin <= 8 (the discriminator's
+ * first layer, models/discriminator.py:301) as a direct gather -- no zero-stuffed tensor, no MFMA tile padded to 32 columns:
+ *   gx[b][t][h][w][ci] = sum over taps (kt,kh,kw) and co of gy[b][ot][oh][ow][co] W[co][ci][kt][kh][kw],  ot = (t + 1 - kt) / 2 where
+ *   t + 1 - kt is even and 0 <= ot < To; oh, ow alike (an even coordinate has one live tap per axis, an odd one two).
+ * gy: [B][To][Ho][Wo] pixels of gy_pix_stride elements (>= Cout, a multiple of 8; channels >= Cout are never read), of `dtype`;
+ * w_table: fp32 [27][Cout][8], entry [(kt*3+kh)*3+kw][co][ci] = W[co][ci][kt][kh][kw], zero for ci >= Cin; gx: [B][T][H][W][8] of `dtype`,
+ * channels >= Cin written as zero.  To, Ho, Wo must equal (T-1)/2+1, (H-1)/2+1, (W-1)/2+1 (else CVVAE_EINVAL).  fp32 FMAs in a fixed
+ * order, one rounding, no atomics: bit-reproducible.  Cin > 8, Cout % 8 != 0, 27 * Cout * (Cin <= 4 ? 4 : 8) * 4 bytes > 64 KiB of LDS
+ * (Cout <= 144 for Cin <= 4, <= 72 else), a stride that is no multiple of 8 or pointers not 16-byte aligned: CVVAE_EUNSUPPORTED.
+ * An addition to ABI 14.
+ */
+int cvvae_conv333_s2_dgrad_small(int32_t dtype, const void* gy, int64_t gy_pix_stride, const float* w_table, void* gx, int64_t B,
+                                 int32_t T, int32_t H, int32_t W, int32_t To, int32_t Ho, int32_t Wo, int32_t Cin, int32_t Cout,
+                                 void* stream);
+
 int cvvae_abi_version(void);
 /* name of the kernel instance cvvae_conv_fwd would launch for d (for profiling reports); NULL if unsupported */
 const char* cvvae_conv_kernel_name(const cvvae_conv_desc* d);
