@@ -46,13 +46,29 @@ class ConvDesc(ctypes.Structure):
     ]
 
 
+MT_CHUNK = 8192  # CVVAE_MT_CHUNK: elements per chunk of the multi-tensor passes
+
+
+class MTChunk(ctypes.Structure):
+    """mirror of `cvvae_mt_chunk` (include/cvvae.h)"""
+
+    _fields_ = [("start", ctypes.c_int64), ("tensor", ctypes.c_int32), ("n", ctypes.c_int32)]
+
+
+class MTTensor(ctypes.Structure):
+    """mirror of `cvvae_mt_tensor` (include/cvvae.h)"""
+
+    _fields_ = [("g", ctypes.c_void_p), ("p", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
+                ("shadow", ctypes.c_void_p), ("step_size", ctypes.c_float), ("bias2_sqrt", ctypes.c_float)]
+
+
 class ReduceShape(ctypes.Structure):
     """mirror of `cvvae_reduce_shape` (include/cvvae.h)"""
 
     _fields_ = [("n", ctypes.c_int64 * 3), ("L", ctypes.c_int64), ("sa", ctypes.c_int64 * 3), ("sb", ctypes.c_int64 * 3)]
 
 
-_vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+_vp, _i32, _i64, _f32, _f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 
 # name -> (restype, argtypes): every symbol include/cvvae.h declares
 PROTOTYPES = {
@@ -123,6 +139,11 @@ PROTOTYPES = {
     "cvvae_avgpool3d_down_stats": (_i32, [_i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "cvvae_gn_leaky_apply_stats": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _f32, _i32, _vp, _vp]),
     "cvvae_conv333_s2_dgrad_small": (_i32, [_i32, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "cvvae_mt_workspace_bytes": (ctypes.c_size_t, [_i64]),
+    "cvvae_mt_grad_norm": (_i32, [_i32, _vp, _vp, _i64, _f32, _vp, _vp, _vp]),
+    "cvvae_mt_scale": (_i32, [_i32, _vp, _vp, _i64, _vp, _vp]),
+    "cvvae_mt_adamw": (_i32, [_i32, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _vp, _vp]),
+    "cvvae_mt_ema": (_i32, [_i32, _vp, _vp, _i64, _f32, _vp]),
 }
 
 _lib = None
@@ -130,7 +151,7 @@ _lib = None
 
 # translation units whose kernels only run in training (weight gradients, channel sums, their reductions): no launch of an
 # encode / decode step comes from them, so the counters of the inference bench do not go stale when they change
-TRAINING_ONLY_SOURCES = ("wgrad_kernel.hip", "loss_kernels.hip", "disc_kernels.hip")
+TRAINING_ONLY_SOURCES = ("wgrad_kernel.hip", "loss_kernels.hip", "disc_kernels.hip", "optim_kernels.hip")
 
 
 def source_fingerprint() -> str:

@@ -1264,3 +1264,137 @@ def conv333_s2_dgrad_small(gy: torch.Tensor, w: torch.Tensor, in_shape, cin: int
                                              oshape[1], oshape[2], oshape[3], int(cin), cout, _stream(gy)),
             "cvvae_conv333_s2_dgrad_small")
     return out
+
+
+# ---- the parameter update: multi-tensor passes over a list of fp32 tensors (include/cvvae.h cvvae_mt_*; cvvae_amd/optim.py) ----
+MT_FIELDS = ("g", "p", "m", "v", "shadow")
+_MT_RING = 4  # pinned staging buffers: the host may queue this many uploads before it has to wait for the oldest copy
+
+
+class MultiTensorList:
+    """the two device tables of the cvvae_mt_* passes for one list of tensors: the chunk table (built once from the element counts)
+    and the pointer table (cvvae_mt_tensor per tensor).  set() reads the tensors' data_ptr()s into a host image and uploads it --
+    through a pinned buffer, with ONE asynchronous copy on the current stream -- only when it differs from what the device holds:
+    gradient pointers move after every zero_grad(set_to_none=True), parameter / moment / shadow pointers do not.  The tensors are
+    the caller's to vouch for (contiguous, fp32, on `device`, as many elements as at construction); the list keeps them alive until
+    the next set() or release().  Launches that read the tables must go to the stream set() ran on."""
+
+    def __init__(self, numels, device, dtype: torch.dtype = torch.float32):
+        import numpy as np
+        self.device, self.dtype = torch.device(device), dtype
+        numels = np.asarray(list(numels), dtype=np.int64)
+        self.numels = numels
+        self.n_tensors = int(numels.size)
+        counts = (numels + (L.MT_CHUNK - 1)) // L.MT_CHUNK
+        self.n_chunks = int(counts.sum())
+        if self.n_tensors >= 2 ** 31 or self.n_chunks >= 2 ** 31:
+            raise ValueError("MultiTensorList: too many tensors / chunks")
+        tensor = np.repeat(np.arange(self.n_tensors, dtype=np.int64), counts)
+        first = np.repeat(np.cumsum(counts) - counts, counts)
+        chunks = np.zeros(max(self.n_chunks, 1), dtype=np.dtype([("start", "<i8"), ("tensor", "<i4"), ("n", "<i4")]))
+        assert chunks.dtype.itemsize == ctypes.sizeof(L.MTChunk)
+        start = (np.arange(self.n_chunks, dtype=np.int64) - first) * L.MT_CHUNK
+        chunks["start"][:self.n_chunks] = start
+        chunks["tensor"][:self.n_chunks] = tensor
+        chunks["n"][:self.n_chunks] = np.minimum(numels[tensor] - start, L.MT_CHUNK)
+        self.chunks = torch.from_numpy(chunks.view(np.int64).reshape(-1, 2)).to(self.device)
+        words = ctypes.sizeof(L.MTTensor) // 8
+        rows = max(self.n_tensors, 1)
+        self._image = np.zeros((rows, words), dtype=np.int64)      # what the next launch needs
+        self._on_device = None                                     # what the device table holds
+        pin = self.device.type == "cuda" and torch.cuda.is_available()
+        self._ring = [torch.zeros((rows, words), dtype=torch.int64, pin_memory=pin) for _ in range(_MT_RING if pin else 1)]
+        self._events = [None] * len(self._ring)
+        self._turn = 0
+        self.table = torch.zeros((rows, words), dtype=torch.int64, device=self.device)
+        self.uploads = 0
+        self.tensors = {}
+        self.step_size = self.bias2_sqrt = None
+
+    def set(self, step_size=None, bias2_sqrt=None, **fields) -> "MultiTensorList":
+        """fields: g / p / m / v / shadow = a sequence of n_tensors tensors each; step_size / bias2_sqrt: n_tensors floats (cvvae_mt_adamw's
+        per-tensor scalars).  Fields not given keep their last value."""
+        import numpy as np
+        img = self._image
+        for f, ts in fields.items():
+            col = MT_FIELDS.index(f)
+            if len(ts) != self.n_tensors:
+                raise ValueError(f"MultiTensorList.set: {len(ts)} tensors for field {f!r} of a list of {self.n_tensors}")
+            img[:self.n_tensors, col] = [t.data_ptr() for t in ts]
+            self.tensors[f] = ts
+        if step_size is not None:
+            scal = img.view(np.float32)
+            scal[:self.n_tensors, 2 * len(MT_FIELDS)] = step_size
+            scal[:self.n_tensors, 2 * len(MT_FIELDS) + 1] = bias2_sqrt
+            self.step_size, self.bias2_sqrt = step_size, bias2_sqrt
+        if self._on_device is None or not np.array_equal(img, self._on_device):
+            self._upload(img)
+            self._on_device = img.copy()
+        return self
+
+    def release(self, *fields):
+        """drop the references to the tensors of `fields` (gradients after the launches that read them: launches and frees are ordered
+        on the stream, and a list that kept them would hold a second copy of every gradient across zero_grad)"""
+        for f in fields:
+            self.tensors.pop(f, None)
+
+    def _upload(self, img):
+        """one asynchronous copy of the host image to the device table, through the next pinned buffer of the ring"""
+        i = self._turn
+        self._turn = (i + 1) % len(self._ring)
+        if self._events[i] is not None:
+            self._events[i].synchronize()  # the copy that last read this buffer (_MT_RING uploads ago)
+        self._ring[i].numpy()[...] = img
+        self.table.copy_(self._ring[i], non_blocking=True)
+        if self._ring[i].is_pinned():
+            self._events[i] = torch.cuda.Event()
+            self._events[i].record(torch.cuda.current_stream(self.device))
+        self.uploads += 1
+
+
+def _mt_args(mtl: MultiTensorList, need):
+    _need_gpu(mtl.table)
+    missing = [f for f in need if f not in mtl.tensors]
+    if missing:
+        raise ValueError(f"MultiTensorList: fields {missing} were never set")
+    return L.load(), _dt(mtl.dtype), mtl.chunks.data_ptr(), mtl.table.data_ptr(), mtl.n_chunks
+
+
+def _mt_coef(coef: torch.Tensor, mtl: MultiTensorList):
+    if coef.dtype != torch.float32 or coef.numel() != 1 or coef.device != mtl.table.device:
+        raise ValueError("the clip coefficient is one fp32 element on the list's device")
+    return coef.data_ptr()
+
+
+def mt_grad_norm(mtl: MultiTensorList, max_norm: float) -> torch.Tensor:
+    """-> fp32 DEVICE tensor [2]: the L2 norm of all the list's gradients taken together, and coef = min(1, max_norm / (norm + 1e-6))
+    (NaN stays NaN).  Deterministic: no atomics, one partial per chunk merged in chunk order.  No host synchronisation."""
+    lib, dt, chunks, table, n = _mt_args(mtl, ("g",))
+    ws = torch.empty(int(lib.cvvae_mt_workspace_bytes(n)), dtype=torch.uint8, device=mtl.table.device)
+    out2 = torch.empty(2, dtype=torch.float32, device=mtl.table.device)
+    L.check(lib.cvvae_mt_grad_norm(dt, chunks, table, n, float(max_norm), ws.data_ptr(), out2.data_ptr(), _stream(mtl.table)),
+            "cvvae_mt_grad_norm")
+    return out2
+
+
+def mt_scale(mtl: MultiTensorList, coef: torch.Tensor) -> None:
+    """g <- coef g in place over the list; coef: one fp32 DEVICE element"""
+    lib, dt, chunks, table, n = _mt_args(mtl, ("g",))
+    L.check(lib.cvvae_mt_scale(dt, chunks, table, n, _mt_coef(coef, mtl), _stream(mtl.table)), "cvvae_mt_scale")
+
+
+def mt_adamw(mtl: MultiTensorList, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
+             coef: Optional[torch.Tensor] = None) -> None:
+    """torch.optim.AdamW's step over the list (p, m, v updated in place from g; include/cvvae.h cvvae_mt_adamw), with the gradients
+    read as coef g when coef (one fp32 DEVICE element) is given; the per-tensor step_size / bias2_sqrt come from MultiTensorList.set"""
+    lib, dt, chunks, table, n = _mt_args(mtl, ("g", "p", "m", "v"))
+    if mtl.step_size is None:
+        raise ValueError("MultiTensorList: step_size / bias2_sqrt were never set")
+    L.check(lib.cvvae_mt_adamw(dt, chunks, table, n, float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                               _mt_coef(coef, mtl) if coef is not None else None, _stream(mtl.table)), "cvvae_mt_adamw")
+
+
+def mt_ema(mtl: MultiTensorList, one_minus_decay: float) -> None:
+    """shadow <- shadow - one_minus_decay (shadow - p) over the list"""
+    lib, dt, chunks, table, n = _mt_args(mtl, ("p", "shadow"))
+    L.check(lib.cvvae_mt_ema(dt, chunks, table, n, float(one_minus_decay), _stream(mtl.table)), "cvvae_mt_ema")

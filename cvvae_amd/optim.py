@@ -1,0 +1,174 @@
+"""The parameter update of a training iteration on the HIP kernels: gradient-norm clip + AdamW in two sweeps.
+
+`AdamW` is `torch.optim.AdamW` with its step on the multi-tensor kernels of include/cvvae.h (cvvae_mt_grad_norm, cvvae_mt_adamw):
+same constructor, same state, same state_dict -- `optimizer_config.target: cvvae_amd.optim.AdamW` takes the yaml's params as they
+are.  One extra keyword, `max_grad_norm`, folds `clip_gradients(opt, max_grad_norm, "norm")` into the step: the norm of ALL groups'
+gradients is reduced on the device, and the AdamW pass reads the clip coefficient from device memory and applies it in flight.
+Nothing synchronises with the host.
+
+Differences from clip_grad_norm_ + torch.optim.AdamW.step:
+  * with max_grad_norm the gradients are LEFT UNSCALED (`p.grad` after step() is what backward wrote); the moments and the
+    parameters see the clipped ones.  Use `clip_grad_norm_` below where the scaled gradients themselves are wanted;
+  * the total norm is `optimizer.last_grad_norm`, a 0-dim device tensor (for logging), not a return value;
+  * the arithmetic is fp32 in another order (fused multiply-adds; beta m + (1 - beta) g instead of lerp): results agree with torch's to a
+    few ulp (tests/test_gpu_optim.py), not bit for bit.
+
+A param group runs on the kernels when every parameter of it that has a gradient is a dense, contiguous fp32 tensor on a ROCm device
+(and `fused` was not asked for); any other group -- CPU tensors, 16-bit parameters, for which torch keeps 16-bit moments -- takes
+torch's own path unchanged.  amsgrad / maximize / capturable / differentiable have no kernel: a group that asks for one and holds a
+parameter the kernels would take is refused at construction."""
+import math
+from typing import Iterable, List, Optional, Union
+
+import torch
+
+from . import ops
+
+_NO_KERNEL = ("amsgrad", "maximize", "capturable", "differentiable")
+
+
+def _kernel_tensor(t: torch.Tensor) -> bool:
+    return t.is_cuda and t.dtype == torch.float32 and not t.is_sparse and t.is_contiguous()
+
+
+class _Lists:
+    """MultiTensorLists by the identity of the tensors they were built for (the chunk table depends on the element counts alone, but
+    a list is one launch's pointer table: two parameter sets must not share one)"""
+
+    def __init__(self, keep: int = 8):
+        self.keep, self.d = keep, {}
+
+    def get(self, tag, tensors) -> "ops.MultiTensorList":
+        key = (tag,) + tuple(id(t) for t in tensors)
+        hit = self.d.get(key)
+        if hit is None or [int(n) for n in hit.numels] != [t.numel() for t in tensors]:
+            if len(self.d) >= self.keep:
+                self.d.pop(next(iter(self.d)))
+            hit = self.d[key] = ops.MultiTensorList([t.numel() for t in tensors], tensors[0].device if tensors else "cpu")
+        return hit
+
+
+class AdamW(torch.optim.AdamW):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
+                 foreach=None, capturable=False, differentiable=False, fused=None, max_grad_norm: Optional[float] = None):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.last_grad_norm: Optional[torch.Tensor] = None
+        self._lists = _Lists()
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
+                         foreach=foreach, capturable=capturable, differentiable=differentiable, fused=fused)
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        g = self.param_groups[-1]
+        asked = [k for k in _NO_KERNEL if g.get(k)]
+        if asked and not g.get("fused") and any(p.is_cuda and p.dtype == torch.float32 for p in g["params"]):
+            self.param_groups.pop()
+            raise NotImplementedError(f"cvvae_amd.optim.AdamW: no HIP kernel for {', '.join(asked)}=True on fp32 device parameters; "
+                                      "use torch.optim.AdamW for this group")
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.__dict__.setdefault("max_grad_norm", None)
+        self.__dict__.setdefault("last_grad_norm", None)
+        self._lists = _Lists()
+
+    def _on_kernels(self, group) -> bool:
+        if group.get("fused") or any(group.get(k) for k in _NO_KERNEL) or torch.is_tensor(group["lr"]):
+            return False
+        seen = None
+        for p in group["params"]:
+            g = p.grad
+            if g is None:
+                continue
+            if g.is_sparse:
+                raise RuntimeError("Adam does not support sparse gradients, please consider SparseAdam instead")
+            if not (_kernel_tensor(p) and _kernel_tensor(g) and g.device == p.device and seen in (None, p.device)):
+                return False
+            seen = p.device
+        return seen is not None
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        groups = self.param_groups
+        on_kernels = [self._on_kernels(g) for g in groups]
+        coef = None
+        if self.max_grad_norm is not None:
+            with_grad = [p for g in groups for p in g["params"] if p.grad is not None]
+            devices = {p.device for p in with_grad}
+            if with_grad and len(devices) == 1 and all(k or not any(p.grad is not None for p in g["params"]) for k, g in zip(on_kernels, groups)):
+                mtl = self._lists.get("norm", with_grad).set(g=[p.grad for p in with_grad])
+                out2 = ops.mt_grad_norm(mtl, self.max_grad_norm)
+                mtl.release("g")
+                self.last_grad_norm, coef = out2[0], out2[1]
+            elif with_grad:
+                # a group the kernels do not take: torch's clip (it scales the gradients in place), then unclipped steps
+                self.last_grad_norm = torch.nn.utils.clip_grad_norm_(with_grad, self.max_grad_norm)
+        for group, k in zip(groups, on_kernels):
+            if k:
+                self._kernel_step(group, coef)
+            elif any(p.grad is not None for p in group["params"]):
+                self._torch_step(group)
+        return loss
+
+    def _kernel_step(self, group, coef):
+        params: List[torch.Tensor] = []
+        grads: List[torch.Tensor] = []
+        exp_avgs: List[torch.Tensor] = []
+        exp_avg_sqs: List[torch.Tensor] = []
+        steps: List[torch.Tensor] = []
+        self._init_group(group, params, grads, exp_avgs, exp_avg_sqs, [], steps)   # torch's own lazy state
+        torch._foreach_add_(steps, 1)
+        beta1, beta2 = (float(b) for b in group["betas"])
+        lr = float(group["lr"])
+        t = torch.stack(steps).tolist()                                            # CPU tensors: no device synchronisation
+        step_size = [lr / (1.0 - beta1 ** s) for s in t]
+        bias2_sqrt = [math.sqrt(1.0 - beta2 ** s) for s in t]
+        mtl = self._lists.get(id(group["params"]), params)
+        mtl.set(step_size=step_size, bias2_sqrt=bias2_sqrt, g=grads, p=params, m=exp_avgs, v=exp_avg_sqs)
+        ops.mt_adamw(mtl, lr, beta1, beta2, float(group["eps"]), float(group["weight_decay"]), coef)
+        mtl.release("g")
+        # every other writer of a parameter moves its version counter: the weight caches, the autocast copies and grad3d's
+        # forward / backward check key on it
+        torch.autograd.graph.increment_version(params)
+
+    def _torch_step(self, group):
+        """torch.optim.AdamW.step for this one group"""
+        fn = torch.optim.AdamW.step
+        while getattr(fn, "hooked", False):       # Optimizer's hook wrapper, when the base class has been instantiated: the hooks
+            fn = fn.__wrapped__                   # have run around OUR step already
+        keep = self.param_groups
+        self.param_groups = [group]
+        try:
+            fn(self)
+        finally:
+            self.param_groups = keep
+
+
+_clip_lists = _Lists(keep=4)
+
+
+def clip_grad_norm_(parameters: Union[torch.Tensor, Iterable[torch.Tensor]], max_norm: float, norm_type: float = 2.0,
+                    error_if_nonfinite: bool = False, foreach: Optional[bool] = None) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ for norm_type 2 on the kernels: the gradients are scaled in place by min(1, max_norm / (norm +
+    1e-6)) and the total norm comes back as a 0-dim device tensor; two sweeps, no host synchronisation.  Gradients that are not all
+    dense contiguous fp32 tensors on one ROCm device, another norm_type or error_if_nonfinite (which has to look at the norm on the
+    host) go to torch's own function."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    ps = [p for p in parameters if p.grad is not None]
+    grads = [p.grad for p in ps]
+    if (not grads or float(norm_type) != 2.0 or error_if_nonfinite or len({g.device for g in grads}) != 1
+            or not all(_kernel_tensor(g) for g in grads)):
+        return torch.nn.utils.clip_grad_norm_(ps, max_norm, norm_type, error_if_nonfinite, foreach)
+    mtl = _clip_lists.get("clip", ps).set(g=grads)
+    out2 = ops.mt_grad_norm(mtl, float(max_norm))
+    ops.mt_scale(mtl, out2[1])
+    mtl.release("g")
+    torch.autograd.graph.increment_version(grads)
+    return out2[0]

@@ -592,6 +592,58 @@ int cvvae_conv333_s2_dgrad_small(int32_t dtype, const void* gy, int64_t gy_pix_s
                                  int32_t T, int32_t H, int32_t W, int32_t To, int32_t Ho, int32_t Wo, int32_t Cin, int32_t Cout,
                                  void* stream);
 
+/*
+ * The parameter update of a training iteration (cvvae_amd/optim.py, lvdm/modules/ema.py; csrc/optim_kernels.hip): gradient-norm clip,
+ * AdamW and the EMA of the weights as multi-tensor passes over a LIST of contiguous fp32 tensors.  Additions to ABI 14: no existing
+ * entry point or struct changed, so the version number stays.
+ *
+ * The list is two DEVICE tables.  `chunks` [n_chunks]: entry c covers elements [start, start + n) of tensor `tensor`, 0 < n <=
+ * CVVAE_MT_CHUNK, start a multiple of CVVAE_MT_CHUNK; the chunks of a tensor partition it (an empty tensor has none), tensors in list
+ * order, chunks in element order -- the caller builds them, the kernels trust them.  `tensors`: per tensor the base pointers (only those
+ * an entry point names are read; 4-byte alignment is enough, 16-byte aligned operands move as 16-byte vectors) and two scalars of
+ * cvvae_mt_adamw.  One workgroup per chunk; every element has one writer and nothing is atomic.  dtype is the tensors' and must be
+ * CVVAE_F32 (else CVVAE_EUNSUPPORTED); n_chunks = 0 is allowed (tables may then be NULL), n_chunks > CVVAE_MT_MAX_CHUNKS is CVVAE_EINVAL.
+ *
+ * cvvae_mt_grad_norm (reads g): out2[0] = the L2 norm of all listed gradients taken together; out2[1] = coef = min(1, max_norm /
+ * (norm + 1e-6)) in fp32 -- torch.nn.utils.clip_grad_norm_'s arithmetic, clamp(max = 1) included: a NaN norm gives a NaN coef (an
+ * infinite one gives 0, as there).  Sum of squares in a fixed order: within a thread in index order (groups of 8), a butterfly over the
+ * wave, the four waves through LDS in wave order, ONE partial per chunk in `workspace` (cvvae_mt_workspace_bytes, pure host code); a
+ * one-workgroup second stage merges the partials in chunk order.  The result is a function of the values and the list order alone.
+ * cvvae_mt_scale: g <- coef g in place, coef read from a DEVICE fp32 scalar.
+ * cvvae_mt_adamw (reads g; updates p, m, v): torch.optim.AdamW's decoupled-weight-decay step with G = coef g (coef_dev NULL: G = g;
+ * g itself is not written):
+ *   m <- beta1 m + (1 - beta1) G;   v <- beta2 v + (1 - beta2) G^2;
+ *   p <- p (1 - lr weight_decay) - step_size m / (sqrt(v) / bias2_sqrt + eps)
+ * with the PER-TENSOR step_size = lr / (1 - beta1^t) and bias2_sqrt = sqrt(1 - beta2^t) of its own step count t, computed by the
+ * caller in double: tensors at different t share a launch.  The hyper-parameters are doubles, rounded to fp32 once after 1 - x.
+ * cvvae_mt_ema (reads p; updates shadow): s <- s - one_minus_decay (s - p).
+ */
+#define CVVAE_MT_CHUNK 8192                 /* elements; a multiple of the loss kernels' 2048-element tile */
+#define CVVAE_MT_MAX_CHUNKS (1LL << 31)
+typedef struct cvvae_mt_chunk {
+  int64_t start;  /* first element, within the tensor */
+  int32_t tensor; /* index into the tensor table */
+  int32_t n;      /* elements */
+} cvvae_mt_chunk;
+typedef struct cvvae_mt_tensor {
+  void* g;      /* gradient */
+  void* p;      /* parameter */
+  void* m;      /* exp_avg */
+  void* v;      /* exp_avg_sq */
+  void* shadow; /* EMA of p */
+  float step_size;
+  float bias2_sqrt;
+} cvvae_mt_tensor;
+size_t cvvae_mt_workspace_bytes(int64_t n_chunks);
+int cvvae_mt_grad_norm(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float max_norm,
+                       void* workspace, float* out2, void* stream);
+int cvvae_mt_scale(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, const float* coef_dev,
+                   void* stream);
+int cvvae_mt_adamw(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, double lr, double beta1,
+                   double beta2, double eps, double weight_decay, const float* coef_dev, void* stream);
+int cvvae_mt_ema(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float one_minus_decay,
+                 void* stream);
+
 int cvvae_abi_version(void);
 /* name of the kernel instance cvvae_conv_fwd would launch for d (for profiling reports); NULL if unsupported */
 const char* cvvae_conv_kernel_name(const cvvae_conv_desc* d);

@@ -1,0 +1,201 @@
+"""Time the parameter update of one training iteration on an MI355X: clip_gradients(1.0, "norm") + AdamW step + LitEma, on the
+parameter set of CVVAESD3Model (encoder + decoder, fp32, random gradients) and of the configured discriminator, as
+  (a) `hip`:     cvvae_amd.optim.AdamW(max_grad_norm=1.0).step() + lvdm.modules.ema.LitEma (csrc/optim_kernels.hip);
+  (b) `foreach`: torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW(foreach=True) + the per-parameter EMA loop of the training code
+                 (decay = min(decay, (1 + n) / (10 + n)) on device tensors, then shadow.sub_(one_minus_decay * (shadow - p)) per tensor);
+  (c) `fused`:   the same with torch.optim.AdamW(fused=True), where torch accepts it;
+the three taking turns call by call in ONE process, each with its own parameters, moments, shadows and gradients.
+
+    timeout -k 10 600 python tools/update_step.py                 # writes profiles/update_step.json
+
+Each figure is the median over `--iters` updates of the time between two device events around the update (so host time that the
+device does not hide is in it), after `--warmup` untimed updates.  The three passes of (a) are also timed alone, for the achieved
+bytes/s of each kernel: 4 (norm) + 28 (AdamW) + 12 (EMA) = 44 bytes per parameter is what the update has to move, against 6.3e12
+bytes/s of achievable HBM bandwidth.  Launches of (a) are counted at the wrappers (cvvae_mt_grad_norm is two kernels, the others one;
+plus the pointer-table copies and LitEma's num_updates increment); torch's are not counted here (a kernel trace is a run of its
+own).  There is no CPU path.  No speed bar is asserted; the figures are recorded."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn as nn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from cvvae_amd import _lib, ops  # noqa: E402
+from cvvae_amd.optim import AdamW  # noqa: E402
+from lvdm.modules.ema import LitEma  # noqa: E402
+
+HBM_BYTES_PER_S = 6.3e12
+BYTES_PER_PARAM = {"grad_norm": 4, "adamw": 28, "ema": 12}
+# configs/cvvae_sd3_constraint_training.yaml: optimizer_config.params; base_learning_rate x lr_g_factor
+ADAMW = dict(lr=4.0e-5, betas=[0.9, 0.98], eps=1.0e-4, weight_decay=0.01)
+
+
+class Params(nn.Module):
+    """a bare parameter set with the shapes of a network's parameters"""
+
+    def __init__(self, shapes, gen):
+        super().__init__()
+        self.params = nn.ParameterList([nn.Parameter(torch.randn(s, generator=gen) * 0.05) for s in shapes])
+
+
+def loop_ema(params, shadows, decay, num_updates):
+    """the per-parameter update of the training code's LitEma.forward, on device tensors (with its host read of the decay)"""
+    num_updates += 1
+    d = min(decay, (1 + num_updates) / (10 + num_updates))
+    one_minus_decay = 1.0 - d
+    with torch.no_grad():
+        for p, s in zip(params, shadows):
+            s.sub_(one_minus_decay * (s - p))
+
+
+def count_launches(update):
+    """kernels and copies one update of path (a) queues, counted at the wrappers"""
+    count = [0]
+    saved = {n: getattr(ops, n) for n in ("mt_grad_norm", "mt_adamw", "mt_ema")}
+    saved_upload = ops.MultiTensorList._upload
+
+    def wrap(f, k):
+        def g(*a, **kw):
+            count[0] += k
+            return f(*a, **kw)
+        return g
+    try:
+        for n, k in (("mt_grad_norm", 2), ("mt_adamw", 1), ("mt_ema", 1)):
+            setattr(ops, n, wrap(saved[n], k))
+        ops.MultiTensorList._upload = wrap(saved_upload, 1)
+        update()
+        torch.cuda.synchronize()
+    finally:
+        for n, f in saved.items():
+            setattr(ops, n, f)
+        ops.MultiTensorList._upload = saved_upload
+    return count[0]
+
+
+def timed(fns, warmup, iters):
+    """median device-event ms of each callable, the callables taking turns"""
+    for _ in range(warmup):
+        for f in fns.values():
+            f()
+    torch.cuda.synchronize()
+    ts = {k: [] for k in fns}
+    for _ in range(iters):
+        for k, f in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            e1.synchronize()
+            ts[k].append(e0.elapsed_time(e1))
+    return {k: {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v), "iters": iters} for k, v in ts.items()}
+
+
+def rates(run, n_params, bytes_per_param):
+    run["bytes_per_param"] = bytes_per_param
+    run["achieved_bytes_per_s"] = bytes_per_param * n_params / (run["median_ms"] * 1e-3)
+    run["frac_of_hbm"] = run["achieved_bytes_per_s"] / HBM_BYTES_PER_S
+    return run
+
+
+def measure(shapes, warmup, iters):
+    gen = torch.Generator().manual_seed(5)
+    n_params = sum(int(torch.Size(s).numel()) for s in shapes)
+    out = {"parameters": n_params, "tensors": len(shapes), "chunks": sum(-(-int(torch.Size(s).numel()) // _lib.MT_CHUNK) for s in shapes)}
+    sets = {}
+    for path in ("hip", "foreach", "fused"):
+        net = Params(shapes, torch.Generator().manual_seed(6)).cuda()
+        for p in net.parameters():
+            p.grad = (torch.randn(p.shape, generator=gen) * 0.01).cuda()
+        sets[path] = net
+    fns, launches = {}, {}
+
+    hip = sets["hip"]
+    opt = AdamW(hip.parameters(), max_grad_norm=1.0, **ADAMW)
+    ema = LitEma(hip)
+    def hip_update():
+        opt.step()
+        ema(hip)
+    fns["hip"] = hip_update
+
+    for path, kw in (("foreach", dict(foreach=True)), ("fused", dict(fused=True))):
+        net = sets[path]
+        try:
+            t_opt = torch.optim.AdamW(net.parameters(), **ADAMW, **kw)
+        except (RuntimeError, ValueError) as e:
+            out[path] = {"refused": str(e)}
+            continue
+        ps = list(net.parameters())
+        shadows = [p.detach().clone() for p in ps]
+        decay, num_updates = torch.tensor(0.9999, device="cuda"), torch.tensor(0, dtype=torch.int, device="cuda")
+
+        def torch_update(ps=ps, t_opt=t_opt, shadows=shadows, decay=decay, num_updates=num_updates):
+            torch.nn.utils.clip_grad_norm_(ps, 1.0)
+            t_opt.step()
+            loop_ema(ps, shadows, decay, num_updates)
+        fns[path] = torch_update
+
+    run = timed(fns, warmup, iters)
+    launches["hip"] = count_launches(hip_update) + 1          # + LitEma's num_updates increment
+    for k, v in run.items():
+        out[k] = rates(v, n_params, sum(BYTES_PER_PARAM.values()))
+        out[k]["launches_per_update"] = launches.get(k)
+    best = min((k for k in run if k != "hip"), key=lambda k: run[k]["median_ms"])
+    out["torch_best"] = best
+    out["torch_best_over_hip"] = run[best]["median_ms"] / run["hip"]["median_ms"]
+
+    # the three passes of (a) alone
+    ps = list(hip.parameters())
+    grads = [p.grad for p in ps]
+    st = [opt.state[p] for p in ps]
+    mtl = ops.MultiTensorList([p.numel() for p in ps], "cuda").set(
+        g=grads, p=ps, m=[s["exp_avg"] for s in st], v=[s["exp_avg_sq"] for s in st],
+        shadow=[getattr(ema, ema.m_name2s_name[n]) for n, _ in hip.named_parameters()],
+        step_size=[ADAMW["lr"] / (1 - 0.9 ** 50)] * len(ps), bias2_sqrt=[(1 - 0.98 ** 50) ** 0.5] * len(ps))
+    coef = torch.ones(1, device="cuda")
+    kern = timed({"grad_norm": lambda: ops.mt_grad_norm(mtl, 1.0),
+                  "adamw": lambda: ops.mt_adamw(mtl, ADAMW["lr"], 0.9, 0.98, ADAMW["eps"], ADAMW["weight_decay"], coef),
+                  "ema": lambda: ops.mt_ema(mtl, 1e-4)}, warmup, iters)
+    out["hip_kernels"] = {k: rates(v, n_params, BYTES_PER_PARAM[k]) for k, v in kern.items()}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--sets", default="codec,discriminator")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "update_step.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/update_step.py measures on an MI355X; no GPU found (there is no CPU path)")
+    torch.cuda.set_device(0)
+    import cvvae_amd
+    from cvvae_amd.discriminator import get_cvvae_discriminator
+    res = {"update": "clip_gradients(1.0, 'norm') + AdamW step + LitEma, fp32, yaml hyper-parameters", "warmup": a.warmup,
+           "device": torch.cuda.get_device_name(0), "kernel_sources": _lib.source_fingerprint(), "hbm_bytes_per_s": HBM_BYTES_PER_S,
+           "timing": "device events around each update, paths interleaved in one process", "sets": {}}
+    for name in a.sets.split(","):
+        if name == "codec":
+            m = cvvae_amd.CVVAESD3Model()
+            shapes = [tuple(p.shape) for p in list(m.encoder.parameters()) + list(m.decoder.parameters())]
+        elif name == "discriminator":
+            shapes = [tuple(p.shape) for p in get_cvvae_discriminator().parameters()]
+        else:
+            raise SystemExit(f"unknown parameter set {name!r}")
+        res["sets"][name] = measure(shapes, a.warmup, a.iters)
+        print(name, json.dumps(res["sets"][name]), flush=True)
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
