@@ -223,11 +223,9 @@ extern "C" int cvvae_attention_d512(int32_t dtype, const void* q, const void* k,
   const dim3 grid((unsigned)((N + 127) / 128), (unsigned)batch);
   const float sl2 = scale * 1.4426950408889634f;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CVVAE_BF16)
-    hipLaunchKernelGGL(flash_attn_d512_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)q, (const __bf16*)k, (const __bf16*)vt, (__bf16*)o, N,
-                       (long long)ldvt, sl2);
-  else
-    hipLaunchKernelGGL(flash_attn_d512_kernel<_Float16>, grid, dim3(256), 0, s, (const _Float16*)q, (const _Float16*)k, (const _Float16*)vt,
-                       (_Float16*)o, N, (long long)ldvt, sl2);
-  return (int)hipGetLastError();
+  by_dtype16(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(flash_attn_d512_kernel<T>, grid, dim3(256), 0, s, (const T*)q, (const T*)k, (const T*)vt, (T*)o, N, (long long)ldvt, sl2);
+  });
+  return launch_status();
 }

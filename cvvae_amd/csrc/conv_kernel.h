@@ -34,13 +34,12 @@
 
 #include <type_traits>
 
+#include "pass_common.h"
 #include "tile_map.h"
 
 namespace cvvae {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -304,65 +303,6 @@ struct Geo {
 #endif
   static_assert(NWV == 4 || NPH <= NPIX || NPIX <= PPP, "split");
 };
-
-template <typename T>
-__device__ __forceinline__ void unpack8(const uint4& u, float (&f)[8]) {
-  typename Tr<T>::v8 x = __builtin_bit_cast(typename Tr<T>::v8, u);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) f[j] = (float)x[j];
-}
-template <typename T>
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  typename Tr<T>::v8 x;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) x[j] = (T)f[j];
-  return __builtin_bit_cast(uint4, x);
-}
-
-// 8 consecutive elements <-> fp32 registers, for the 16-bit storage types (one 16-byte access) and for float (two)
-template <typename T>
-struct Raw8 {
-  uint4 a;
-};
-template <>
-struct Raw8<float> {
-  uint4 a, b;
-};
-template <typename T>
-__device__ __forceinline__ Raw8<T> ldraw8(const T* p) {
-  Raw8<T> r;
-  r.a = *reinterpret_cast<const uint4*>(p);
-  return r;
-}
-template <>
-__device__ __forceinline__ Raw8<float> ldraw8<float>(const float* p) {
-  Raw8<float> r;
-  r.a = reinterpret_cast<const uint4*>(p)[0];
-  r.b = reinterpret_cast<const uint4*>(p)[1];
-  return r;
-}
-template <typename T>
-__device__ __forceinline__ void unraw8(const Raw8<T>& r, float (&f)[8]) {
-  unpack8<T>(r.a, f);
-}
-template <>
-__device__ __forceinline__ void unraw8<float>(const Raw8<float>& r, float (&f)[8]) {
-  f[0] = __uint_as_float(r.a.x); f[1] = __uint_as_float(r.a.y); f[2] = __uint_as_float(r.a.z); f[3] = __uint_as_float(r.a.w);
-  f[4] = __uint_as_float(r.b.x); f[5] = __uint_as_float(r.b.y); f[6] = __uint_as_float(r.b.z); f[7] = __uint_as_float(r.b.w);
-}
-template <typename T>
-__device__ __forceinline__ void ld8(const T* p, float (&f)[8]) {
-  unraw8<T>(ldraw8<T>(p), f);
-}
-template <typename T>
-__device__ __forceinline__ void st8(T* p, const float (&f)[8]) {
-  *reinterpret_cast<uint4*>(p) = pack8<T>(f);
-}
-template <>
-__device__ __forceinline__ void st8<float>(float* p, const float (&f)[8]) {
-  reinterpret_cast<float4*>(p)[0] = make_float4(f[0], f[1], f[2], f[3]);
-  reinterpret_cast<float4*>(p)[1] = make_float4(f[4], f[5], f[6], f[7]);
-}
 
 // sum over the 32 lanes of each half-wave, delivered in lanes 31 and 63 (other lanes hold partial sums): four DPP row
 // shifts (zero fill) give lane 15 of every 16-lane row its row sum, row_bcast:15 adds it into the next row (rows 1 and 3)

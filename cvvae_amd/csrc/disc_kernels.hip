@@ -9,10 +9,7 @@
 // along C, then W.  The grid is capped and strides over the groups; group indices are 64-bit.  Every output element has exactly
 // one writer (the adjoint of the pool is a gather), so the results do not depend on the grid: the same inputs give the same bits.
 // In-place calls (y == x, gv == gy) are safe because a lane reads its own 8 elements before it writes them and nobody else's.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/cvvae.h"
+#include "pass_common.h"
 
 namespace cvvae {
 namespace disc {
@@ -21,6 +18,9 @@ constexpr int WG = 256;            // threads per workgroup
 constexpr int VEC = 8;             // elements per lane and trip
 constexpr int MAX_BLOCKS = 2048;   // 8 workgroups per CU; the rest of the tensor is reached by the grid stride
 
+// This file keeps its own 8-element access instead of pass_common.h's ld8 / st8.  The two forms are the same casts in the same
+// 16-byte accesses, but the compiler emits different code for the 16-bit kernels behind them, and with ld8 / st8 the records of
+// gn_leaky_apply_stats_kernel<16-bit, bare> came out different in their last bits (the tensors themselves did not).
 template <typename T>
 __device__ __forceinline__ void load8(const T* p, float (&f)[VEC]) {
   if constexpr (sizeof(T) == 4) {
@@ -204,19 +204,6 @@ __global__ __launch_bounds__(WG) void leaky_bwd_kernel(const T* y, const T* gy, 
 // mean += (m - mean) f,  M2 += m2 + (m - mean)^2 SUB k f,  (m, m2) the exact two-pass statistics of the SUB new values.
 // The slots meet in LDS; group g's thread merges them in a fixed order (pixel lane, then slot): the same inputs give the same bits.
 // ---------------------------------------------------------------------------------------------------------
-struct WStat {
-  float n, mean, m2;
-};
-__device__ __forceinline__ void chan_merge(WStat& a, const WStat& b) {
-  if (b.n == 0.f) return;
-  const float n = a.n + b.n;
-  const float d = b.mean - a.mean;
-  const float f = b.n / n;
-  a.mean += d * f;
-  a.m2 += b.m2 + d * d * a.n * f;
-  a.n = n;
-}
-
 // the value the store leaves in memory
 template <typename T>
 __device__ __forceinline__ void round8(float (&f)[VEC]) {
@@ -431,8 +418,6 @@ static inline int blocks_for(long long ngroups) {
   return (int)(b < MAX_BLOCKS ? b : MAX_BLOCKS);
 }
 
-static inline bool known_dtype(int32_t d) { return d == CVVAE_F16 || d == CVVAE_BF16 || d == CVVAE_F32; }
-
 constexpr long long MAX_ELEMS = 1LL << 40;  // what the index arithmetic above holds with room to spare
 
 // element count of the pool's INPUT [B][T][H][W][C], or -1 when a frame's pixels, the frame count or the total leave their range
@@ -459,12 +444,8 @@ static inline int sub_for(int cpg) { return cpg % 8 == 0 ? 8 : cpg % 4 == 0 ? 4 
 }  // namespace disc
 }  // namespace cvvae
 
+using namespace cvvae;
 using namespace cvvae::disc;
-
-#define DISC_BY_DTYPE(CALL) \
-  do { \
-    if (dtype == CVVAE_F32) { CALL(float); } else if (dtype == CVVAE_F16) { CALL(_Float16); } else { CALL(__bf16); } \
-  } while (0)
 
 extern "C" {
 
@@ -474,12 +455,12 @@ int cvvae_avgpool3d_down(int32_t dtype, const void* x, void* y, int64_t B, int32
   if (pool_elems(B, T, H, W, C) < 0) return CVVAE_EUNSUPPORTED;
   const int To = (T + (T & 1)) / 2, Ho = H / 2, Wo = W / 2;
   const long long ngroups = (long long)B * To * Ho * Wo * (C / VEC);
-#define CALL(TT) \
-  hipLaunchKernelGGL(avgpool3d_down_kernel<TT>, dim3(blocks_for(ngroups)), dim3(WG), 0, (hipStream_t)stream, (const TT*)x, (TT*)y, T, H, \
-                     W, C, To, Ho, Wo, ngroups)
-  DISC_BY_DTYPE(CALL);
-#undef CALL
-  return (int)hipGetLastError();
+  by_dtype(dtype, [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    hipLaunchKernelGGL(avgpool3d_down_kernel<TT>, dim3(blocks_for(ngroups)), dim3(WG), 0, (hipStream_t)stream, (const TT*)x, (TT*)y, T, H,
+                       W, C, To, Ho, Wo, ngroups);
+  });
+  return launch_status();
 }
 
 int cvvae_avgpool3d_down_bwd(int32_t dtype, const void* gy, void* gx, int64_t B, int32_t T, int32_t H, int32_t W, int32_t C,
@@ -490,12 +471,12 @@ int cvvae_avgpool3d_down_bwd(int32_t dtype, const void* gy, void* gx, int64_t B,
   if (total < 0) return CVVAE_EUNSUPPORTED;
   const int To = (T + (T & 1)) / 2, Ho = H / 2, Wo = W / 2;
   const long long ngroups = total / VEC;
-#define CALL(TT) \
-  hipLaunchKernelGGL(avgpool3d_down_bwd_kernel<TT>, dim3(blocks_for(ngroups)), dim3(WG), 0, (hipStream_t)stream, (const TT*)gy, (TT*)gx, \
-                     T, H, W, C, To, Ho, Wo, ngroups)
-  DISC_BY_DTYPE(CALL);
-#undef CALL
-  return (int)hipGetLastError();
+  by_dtype(dtype, [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    hipLaunchKernelGGL(avgpool3d_down_bwd_kernel<TT>, dim3(blocks_for(ngroups)), dim3(WG), 0, (hipStream_t)stream, (const TT*)gy, (TT*)gx,
+                       T, H, W, C, To, Ho, Wo, ngroups);
+  });
+  return launch_status();
 }
 
 int cvvae_gn_leaky_apply(int32_t dtype, const void* x, const float* scale, const float* shift, void* y, int64_t rows, int64_t per_row,
@@ -504,30 +485,28 @@ int cvvae_gn_leaky_apply(int32_t dtype, const void* x, const float* scale, const
   if (!known_dtype(dtype) || C % VEC) return CVVAE_EUNSUPPORTED;
   if (rows > MAX_ELEMS / per_row || rows * per_row > MAX_ELEMS / C) return CVVAE_EUNSUPPORTED;
   const long long ngroups = (long long)rows * per_row * (C / VEC);
-#define CALL(TT) \
-  do { \
-    if (scale) \
-      hipLaunchKernelGGL((gn_leaky_apply_kernel<TT, true>), dim3(blocks_for(ngroups)), dim3(WG), 0, (hipStream_t)stream, (const TT*)x, \
-                         scale, shift, (TT*)y, (long long)per_row, C, slope, ngroups); \
-    else \
-      hipLaunchKernelGGL((gn_leaky_apply_kernel<TT, false>), dim3(blocks_for(ngroups)), dim3(WG), 0, (hipStream_t)stream, (const TT*)x, \
-                         scale, shift, (TT*)y, (long long)per_row, C, slope, ngroups); \
-  } while (0)
-  DISC_BY_DTYPE(CALL);
-#undef CALL
-  return (int)hipGetLastError();
+  by_dtype(dtype, [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    if (scale)
+      hipLaunchKernelGGL((gn_leaky_apply_kernel<TT, true>), dim3(blocks_for(ngroups)), dim3(WG), 0, (hipStream_t)stream, (const TT*)x,
+                         scale, shift, (TT*)y, (long long)per_row, C, slope, ngroups);
+    else
+      hipLaunchKernelGGL((gn_leaky_apply_kernel<TT, false>), dim3(blocks_for(ngroups)), dim3(WG), 0, (hipStream_t)stream, (const TT*)x,
+                         scale, shift, (TT*)y, (long long)per_row, C, slope, ngroups);
+  });
+  return launch_status();
 }
 
 int cvvae_leaky_bwd(int32_t dtype, const void* y, const void* gy, void* gv, int64_t n_elems, float slope, void* stream) {
   if (!y || !gy || !gv || n_elems <= 0 || !(slope > 0.f)) return CVVAE_EINVAL;
   if (!known_dtype(dtype) || n_elems > MAX_ELEMS) return CVVAE_EUNSUPPORTED;
   const long long ngroups = ((long long)n_elems + VEC - 1) / VEC;
-#define CALL(TT) \
-  hipLaunchKernelGGL(leaky_bwd_kernel<TT>, dim3(blocks_for(ngroups)), dim3(WG), 0, (hipStream_t)stream, (const TT*)y, (const TT*)gy, \
-                     (TT*)gv, (long long)n_elems, slope)
-  DISC_BY_DTYPE(CALL);
-#undef CALL
-  return (int)hipGetLastError();
+  by_dtype(dtype, [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    hipLaunchKernelGGL(leaky_bwd_kernel<TT>, dim3(blocks_for(ngroups)), dim3(WG), 0, (hipStream_t)stream, (const TT*)y, (const TT*)gy,
+                       (TT*)gv, (long long)n_elems, slope);
+  });
+  return launch_status();
 }
 
 int64_t cvvae_pass_gn_slabs(int64_t rows, int64_t per_row, int32_t C, int32_t groups) {
@@ -558,11 +537,12 @@ int cvvae_avgpool3d_down_stats(int32_t dtype, const void* x, void* y, int64_t B,
 #define CALL_S(TT, SUB) \
   hipLaunchKernelGGL((avgpool3d_down_stats_kernel<TT, SUB>), dim3((unsigned)slabs, (unsigned)B), dim3(WG), 0, (hipStream_t)stream, \
                      (const TT*)x, (TT*)y, T, H, W, C, To, Ho, Wo, out_groups, out_partials)
-#define CALL(TT) DISC_BY_SUB(CALL_S, TT)
-  DISC_BY_DTYPE(CALL);
-#undef CALL
+  by_dtype(dtype, [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    DISC_BY_SUB(CALL_S, TT);
+  });
 #undef CALL_S
-  return (int)hipGetLastError();
+  return launch_status();
 }
 
 int cvvae_gn_leaky_apply_stats(int32_t dtype, const void* x, const float* scale, const float* shift, void* y, int64_t rows,
@@ -584,11 +564,12 @@ int cvvae_gn_leaky_apply_stats(int32_t dtype, const void* x, const float* scale,
       hipLaunchKernelGGL((gn_leaky_apply_stats_kernel<TT, false, SUB>), dim3((unsigned)slabs, (unsigned)rows), dim3(WG), 0, \
                          (hipStream_t)stream, (const TT*)x, scale, shift, (TT*)y, (long long)per_row, C, slope, out_groups, out_partials); \
   } while (0)
-#define CALL(TT) DISC_BY_SUB(CALL_S, TT)
-  DISC_BY_DTYPE(CALL);
-#undef CALL
+  by_dtype(dtype, [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    DISC_BY_SUB(CALL_S, TT);
+  });
 #undef CALL_S
-  return (int)hipGetLastError();
+  return launch_status();
 }
 
 int cvvae_conv333_s2_dgrad_small(int32_t dtype, const void* gy, int64_t gy_pix_stride, const float* w_table, void* gx, int64_t B,
@@ -610,14 +591,12 @@ int cvvae_conv333_s2_dgrad_small(int32_t dtype, const void* gy, int64_t gy_pix_s
 #define CALL_C(TT, CC) \
   hipLaunchKernelGGL((conv333_s2_dgrad_small_kernel<TT, CC>), dim3(blocks), dim3(WG), (size_t)lds, (hipStream_t)stream, (const TT*)gy, \
                      (long long)gy_pix_stride, w_table, (TT*)gx, T, H, W, To, Ho, Wo, Cout, nchunk, nunits)
-#define CALL(TT) \
-  do { \
-    if (ci == 4) { CALL_C(TT, 4); } else { CALL_C(TT, 8); } \
-  } while (0)
-  DISC_BY_DTYPE(CALL);
-#undef CALL
+  by_dtype(dtype, [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    if (ci == 4) { CALL_C(TT, 4); } else { CALL_C(TT, 8); }
+  });
 #undef CALL_C
-  return (int)hipGetLastError();
+  return launch_status();
 }
 
 }  // extern "C"

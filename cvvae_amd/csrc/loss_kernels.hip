@@ -10,10 +10,7 @@
 // inputs give the same bits on every run, and so do a strided view and its contiguous copy, at any alignment.
 // A group is read with 16-byte loads when it lies inside one inner run and its address is 16-byte aligned, element by element
 // otherwise (the head and tail of a run whose length or base is not a multiple of 8 elements).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/cvvae.h"
+#include "pass_common.h"
 
 namespace cvvae {
 namespace loss {
@@ -22,48 +19,6 @@ constexpr int WG = 256;              // threads per workgroup
 constexpr int VEC = 8;               // elements per group
 constexpr int TILE = WG * VEC;       // elements per workgroup pass
 constexpr int MAX_BLOCKS = 2048;     // stage-1 grid cap = stage-2's serial depth x 256
-
-template <typename T>
-__device__ __forceinline__ bool aligned16(const T* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-template <typename T>
-__device__ __forceinline__ void load8(const T* p, float (&f)[VEC]);
-template <>
-__device__ __forceinline__ void load8<float>(const float* p, float (&f)[VEC]) {
-  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-template <typename T>
-__device__ __forceinline__ void load8_16bit(const T* p, float (&f)[VEC]) {
-  union { uint4 u; T h[VEC]; } v;
-  v.u = *reinterpret_cast<const uint4*>(p);
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) f[j] = (float)v.h[j];
-}
-template <>
-__device__ __forceinline__ void load8<_Float16>(const _Float16* p, float (&f)[VEC]) { load8_16bit<_Float16>(p, f); }
-template <>
-__device__ __forceinline__ void load8<__bf16>(const __bf16* p, float (&f)[VEC]) { load8_16bit<__bf16>(p, f); }
-
-// 8 values rounded once (nearest even) to T, stored as 16-byte vectors when p allows it
-template <typename T>
-__device__ __forceinline__ void store8(T* p, const float (&f)[VEC], int n) {
-  if (n == VEC && aligned16(p)) {
-    if constexpr (sizeof(T) == 4) {
-      reinterpret_cast<float4*>(p)[0] = make_float4(f[0], f[1], f[2], f[3]);
-      reinterpret_cast<float4*>(p)[1] = make_float4(f[4], f[5], f[6], f[7]);
-    } else {
-      union { uint4 u; T h[VEC]; } v;
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) v.h[j] = (T)f[j];
-      *reinterpret_cast<uint4*>(p) = v.u;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < VEC; ++j)
-      if (j < n) p[j] = (T)f[j];
-  }
-}
 
 // up to three outer dimensions (slowest first) with one operand's element strides, and the inner run
 struct View {
@@ -79,13 +34,7 @@ template <typename T>
 __device__ __forceinline__ void gather8(const T* p, const View& v, long long i, int n, float (&f)[VEC]) {
   const long long row = i / v.L, j = i - row * v.L;
   if (n == VEC && j + VEC <= v.L) {
-    const T* q = p + v.offset(row, j);
-    if (aligned16(q)) {
-      load8<T>(q, f);
-    } else {
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) f[k] = (float)q[k];
-    }
+    ld8_n<T>(p + v.offset(row, j), VEC, f);
     return;
   }
 #pragma unroll
@@ -131,16 +80,6 @@ __device__ __forceinline__ float term_grad(int op, float a, float b) {
     case CVVAE_RED_SOFTPLUS_NEG: return -softplus_grad(-a);
     default: return softplus_grad(a);
   }
-}
-
-// workgroup sum in a fixed order, valid in thread 0
-__device__ __forceinline__ float block_sum(float x) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) x += __shfl_xor(x, m, 64);
-  __shared__ float sh[WG / 64];
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-  __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
 
 template <typename TA, typename TB>
@@ -197,11 +136,11 @@ __global__ __launch_bounds__(WG) void reduce_bwd_kernel(int op, const TA* __rest
     }
 #pragma unroll
     for (int k = 0; k < VEC; ++k) g[k] = coef * term_grad(op, fa[k], fb[k]);
-    if (ga) store8<TA>(ga + i, g, n);
+    if (ga) st8_n<TA>(ga + i, g, n);
     if (gb) {
 #pragma unroll
       for (int k = 0; k < VEC; ++k) g[k] = -g[k];
-      store8<TB>(gb + i, g, n);
+      st8_n<TB>(gb + i, g, n);
     }
   }
 }
@@ -226,14 +165,7 @@ __global__ __launch_bounds__(WG) void gauss_reg_kernel(const T* __restrict__ mom
     float m[VEC], lv[VEC], e[VEC], o[VEC];
     gather8<T>(mom, vm, i, n, m);
     gather8<T>(mom + CS, vm, i, n, lv);
-    if (noise) {
-      if (n == VEC && aligned16(noise + i)) {
-        load8<T>(noise + i, e);
-      } else {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) e[k] = (k < n) ? (float)noise[i + k] : 0.f;
-      }
-    }
+    if (noise) ld8_n<T>(noise + i, n, e);
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
@@ -241,7 +173,7 @@ __global__ __launch_bounds__(WG) void gauss_reg_kernel(const T* __restrict__ mom
       o[k] = noise ? __builtin_fmaf(expf(0.5f * l), e[k], m[k]) : m[k];
       s += (k < n) ? (m[k] * m[k] + expf(l) - 1.f - l) : 0.f;
     }
-    store8<T>(z + i, o, n);
+    st8_n<T>(z + i, o, n);
     acc += s;
   }
   acc = block_sum(acc);
@@ -266,20 +198,8 @@ __global__ __launch_bounds__(WG) void gauss_reg_bwd_kernel(const T* __restrict__
 #pragma unroll
     for (int k = 0; k < VEC; ++k) e[k] = g[k] = 0.f;
     if (gz) {
-      if (n == VEC && aligned16(gz + i)) {
-        load8<T>(gz + i, g);
-      } else {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) g[k] = (k < n) ? (float)gz[i + k] : 0.f;
-      }
-      if (noise) {
-        if (n == VEC && aligned16(noise + i)) {
-          load8<T>(noise + i, e);
-        } else {
-#pragma unroll
-          for (int k = 0; k < VEC; ++k) e[k] = (k < n) ? (float)noise[i + k] : 0.f;
-        }
-      }
+      ld8_n<T>(gz + i, n, g);
+      if (noise) ld8_n<T>(noise + i, n, e);
     }
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
@@ -291,8 +211,8 @@ __global__ __launch_bounds__(WG) void gauss_reg_bwd_kernel(const T* __restrict__
     // element i = (b, r) of a chunk lands at b * 2CS + r (mean) and b * 2CS + CS + r (logvar)
     const long long row = i / CS, r = i - row * CS;
     if (n == VEC && r + VEC <= CS) {
-      store8<T>(gmom + row * 2 * CS + r, dm, VEC);
-      store8<T>(gmom + row * 2 * CS + CS + r, dl, VEC);
+      st8_n<T>(gmom + row * 2 * CS + r, dm, VEC);
+      st8_n<T>(gmom + row * 2 * CS + CS + r, dl, VEC);
     } else {
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
@@ -324,33 +244,14 @@ static inline long long shape_total(const cvvae_reduce_shape* s, bool two) {
   return total * s->L;
 }
 
-static inline bool known_dtype(int32_t d) { return d == CVVAE_F16 || d == CVVAE_BF16 || d == CVVAE_F32; }
 static inline bool known_op(int32_t op) { return op >= CVVAE_RED_ABS_DIFF && op <= CVVAE_RED_SOFTPLUS_POS; }
 static inline bool two_operands(int32_t op) { return op == CVVAE_RED_ABS_DIFF || op == CVVAE_RED_SQ_DIFF; }
 
 }  // namespace loss
 }  // namespace cvvae
 
+using namespace cvvae;
 using namespace cvvae::loss;
-
-#define CHECK_LAUNCH() return (int)hipGetLastError()
-
-// CALL(TA, TB) for the pair (dtype_a, dtype_b); both are known dtypes by the time this runs
-#define LOSS_BY_PAIR(CALL) \
-  do { \
-    if (dtype_a == CVVAE_F32) { \
-      if (dtype_b == CVVAE_F32) { CALL(float, float); } else if (dtype_b == CVVAE_F16) { CALL(float, _Float16); } else { CALL(float, __bf16); } \
-    } else if (dtype_a == CVVAE_F16) { \
-      if (dtype_b == CVVAE_F32) { CALL(_Float16, float); } else if (dtype_b == CVVAE_F16) { CALL(_Float16, _Float16); } else { CALL(_Float16, __bf16); } \
-    } else { \
-      if (dtype_b == CVVAE_F32) { CALL(__bf16, float); } else if (dtype_b == CVVAE_F16) { CALL(__bf16, _Float16); } else { CALL(__bf16, __bf16); } \
-    } \
-  } while (0)
-
-#define LOSS_BY_DTYPE(CALL) \
-  do { \
-    if (dtype == CVVAE_F32) { CALL(float); } else if (dtype == CVVAE_F16) { CALL(_Float16); } else { CALL(__bf16); } \
-  } while (0)
 
 extern "C" {
 
@@ -374,13 +275,16 @@ int cvvae_reduce_sum(int32_t op, int32_t dtype_a, const void* a, int32_t dtype_b
   const View vb{shape->n[1], shape->n[2], shape->L, shape->sb[0], shape->sb[1], shape->sb[2]};
   const int nblk = (int)blocks_for(total);
   hipStream_t s = (hipStream_t)stream;
-#define CALL(TA, TB) \
-  hipLaunchKernelGGL((reduce_partial_kernel<TA, TB>), dim3(nblk), dim3(WG), 0, s, op, (const TA*)a, va, (const TB*)b, vb, total, \
-                     (float*)workspace)
-  LOSS_BY_PAIR(CALL);
-#undef CALL
+  by_dtype(dtype_a, [&](auto ta) {
+    by_dtype(dtype_b, [&](auto tb) {
+      using TA = typename decltype(ta)::type;
+      using TB = typename decltype(tb)::type;
+      hipLaunchKernelGGL((reduce_partial_kernel<TA, TB>), dim3(nblk), dim3(WG), 0, s, op, (const TA*)a, va, (const TB*)b, vb, total,
+                         (float*)workspace);
+    });
+  });
   hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(WG), 0, s, (const float*)workspace, nblk, 1.0f, out);
-  CHECK_LAUNCH();
+  return launch_status();
 }
 
 int cvvae_reduce_sum_bwd(int32_t op, int32_t dtype_a, const void* a, int32_t dtype_b, const void* b, const cvvae_reduce_shape* shape,
@@ -398,12 +302,15 @@ int cvvae_reduce_sum_bwd(int32_t op, int32_t dtype_a, const void* a, int32_t dty
   const long long tiles = (total + TILE - 1) / TILE;
   const int nblk = (int)(tiles < 65536 ? tiles : 65536);
   hipStream_t s = (hipStream_t)stream;
-#define CALL(TA, TB) \
-  hipLaunchKernelGGL((reduce_bwd_kernel<TA, TB>), dim3(nblk), dim3(WG), 0, s, op, (const TA*)a, va, (const TB*)b, vb, total, coef_dev, \
-                     (TA*)ga, (TB*)gb)
-  LOSS_BY_PAIR(CALL);
-#undef CALL
-  CHECK_LAUNCH();
+  by_dtype(dtype_a, [&](auto ta) {
+    by_dtype(dtype_b, [&](auto tb) {
+      using TA = typename decltype(ta)::type;
+      using TB = typename decltype(tb)::type;
+      hipLaunchKernelGGL((reduce_bwd_kernel<TA, TB>), dim3(nblk), dim3(WG), 0, s, op, (const TA*)a, va, (const TB*)b, vb, total, coef_dev,
+                         (TA*)ga, (TB*)gb);
+    });
+  });
+  return launch_status();
 }
 
 int cvvae_gauss_reg(int32_t dtype, const void* moments, const void* noise, void* z, int64_t B, int64_t C, int64_t S, void* workspace,
@@ -414,12 +321,13 @@ int cvvae_gauss_reg(int32_t dtype, const void* moments, const void* noise, void*
   const long long CS = (long long)C * S, total = CS * B;
   const int nblk = (int)blocks_for(total);
   hipStream_t s = (hipStream_t)stream;
-#define CALL(T) \
-  hipLaunchKernelGGL(gauss_reg_kernel<T>, dim3(nblk), dim3(WG), 0, s, (const T*)moments, (const T*)noise, (T*)z, CS, total, (float*)workspace)
-  LOSS_BY_DTYPE(CALL);
-#undef CALL
+  by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(gauss_reg_kernel<T>, dim3(nblk), dim3(WG), 0, s, (const T*)moments, (const T*)noise, (T*)z, CS, total,
+                       (float*)workspace);
+  });
   hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(WG), 0, s, (const float*)workspace, nblk, 0.5f, kl_sum);
-  CHECK_LAUNCH();
+  return launch_status();
 }
 
 int cvvae_gauss_reg_bwd(int32_t dtype, const void* moments, const void* noise, const void* g_z, const float* coef_kl_dev,
@@ -431,12 +339,12 @@ int cvvae_gauss_reg_bwd(int32_t dtype, const void* moments, const void* noise, c
   const long long tiles = (total + TILE - 1) / TILE;
   const int nblk = (int)(tiles < 65536 ? tiles : 65536);
   hipStream_t s = (hipStream_t)stream;
-#define CALL(T) \
-  hipLaunchKernelGGL(gauss_reg_bwd_kernel<T>, dim3(nblk), dim3(WG), 0, s, (const T*)moments, (const T*)noise, (const T*)g_z, coef_kl_dev, \
-                     (T*)g_moments, CS, total)
-  LOSS_BY_DTYPE(CALL);
-#undef CALL
-  CHECK_LAUNCH();
+  by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(gauss_reg_bwd_kernel<T>, dim3(nblk), dim3(WG), 0, s, (const T*)moments, (const T*)noise, (const T*)g_z, coef_kl_dev,
+                       (T*)g_moments, CS, total);
+  });
+  return launch_status();
 }
 
 }  // extern "C"

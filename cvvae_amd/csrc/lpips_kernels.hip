@@ -3,11 +3,7 @@
 // (channel-normalise, squared difference, 1x1 lin, spatial mean) forward and backward.  gfx950 only.
 // Every pass reads each tensor once and writes each tensor once, with 16-byte accesses along C; arithmetic is fp32 with one
 // rounding to the storage dtype; no atomics (the head's partial sums are merged in index order).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/cvvae.h"
-#include "conv_kernel.h"
+#include "pass_common.h"
 
 namespace cvvae {
 
@@ -286,7 +282,6 @@ constexpr int HEAD_FWD_BLOCKS = 256, HEAD_BWD_BLOCKS = 2048;
 
 using namespace cvvae;
 
-#define CHECK_LAUNCH() return (int)hipGetLastError()
 static inline unsigned grid_for(long long nvec) {
   long long blocks = (nvec + 255) / 256;
   if (blocks > 256LL * 64) blocks = 256LL * 64;
@@ -302,64 +297,60 @@ int cvvae_lpips_scale_in(int32_t src_dtype, int32_t dst_dtype, const void* in, i
   if ((nvec + 255) / 256 >= (1LL << 31)) return CVVAE_EUNSUPPORTED;
   const dim3 grid((unsigned)((nvec + 255) / 256));
   hipStream_t s = (hipStream_t)stream;
-#define L(TS, TD) \
-  hipLaunchKernelGGL((lpips_scale_in_kernel<TS, TD>), grid, dim3(256), 0, s, (const TS*)in, HW, Cpad / 8, nvec, shift, scale, (TD*)out)
-#define LS(TD) \
-  if (src_dtype == CVVAE_BF16) L(__bf16, TD); \
-  else if (src_dtype == CVVAE_F16) L(_Float16, TD); \
-  else if (src_dtype == CVVAE_F32) L(float, TD); \
-  else return CVVAE_EINVAL
-  if (dst_dtype == CVVAE_BF16) { LS(__bf16); }
-  else if (dst_dtype == CVVAE_F16) { LS(_Float16); }
-  else if (dst_dtype == CVVAE_F32) { LS(float); }
-  else return CVVAE_EINVAL;
-#undef L
-  CHECK_LAUNCH();
+  bool ok = false;
+  by_dtype(dst_dtype, [&](auto td) {
+    ok = by_dtype(src_dtype, [&](auto ts) {
+      using TS = typename decltype(ts)::type;
+      using TD = typename decltype(td)::type;
+      hipLaunchKernelGGL((lpips_scale_in_kernel<TS, TD>), grid, dim3(256), 0, s, (const TS*)in, HW, Cpad / 8, nvec, shift, scale, (TD*)out);
+    });
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_lpips_scale_in_bwd(int32_t g_dtype, int32_t dst_dtype, const void* g, int64_t N, int32_t H, int32_t W, int64_t pix_stride,
                              const float* scale, void* out, void* stream) {
   if (!g || !out || !scale || N <= 0 || H <= 0 || W <= 0 || pix_stride < 8 || pix_stride % 8) return CVVAE_EINVAL;
   const long long HW = (long long)H * W, npix = HW * N;
-  const int32_t src_dtype = g_dtype;
   if ((npix + 255) / 256 >= (1LL << 31)) return CVVAE_EUNSUPPORTED;
   const dim3 grid((unsigned)((npix + 255) / 256));
   hipStream_t s = (hipStream_t)stream;
-#define L(TS, TD) \
-  hipLaunchKernelGGL((lpips_scale_in_bwd_kernel<TS, TD>), grid, dim3(256), 0, s, (const TS*)g, HW, (long long)pix_stride, npix, scale, (TD*)out)
-  if (dst_dtype == CVVAE_BF16) { LS(__bf16); }
-  else if (dst_dtype == CVVAE_F16) { LS(_Float16); }
-  else if (dst_dtype == CVVAE_F32) { LS(float); }
-  else return CVVAE_EINVAL;
-#undef L
-#undef LS
-  CHECK_LAUNCH();
+  bool ok = false;
+  by_dtype(dst_dtype, [&](auto td) {
+    ok = by_dtype(g_dtype, [&](auto ts) {
+      using TS = typename decltype(ts)::type;
+      using TD = typename decltype(td)::type;
+      hipLaunchKernelGGL((lpips_scale_in_bwd_kernel<TS, TD>), grid, dim3(256), 0, s, (const TS*)g, HW, (long long)pix_stride, npix, scale,
+                         (TD*)out);
+    });
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
-
-#define LPIPS_BY_DTYPE(CALL) \
-  if (dtype == CVVAE_BF16) { CALL(__bf16); } \
-  else if (dtype == CVVAE_F16) { CALL(_Float16); } \
-  else if (dtype == CVVAE_F32) { CALL(float); } \
-  else return CVVAE_EINVAL
 
 int cvvae_relu(int32_t dtype, const void* x, int64_t n, void* out, void* stream) {
   if (!x || !out || n <= 0 || n % 8) return CVVAE_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const long long nvec = n / 8;
-#define CALL(T) hipLaunchKernelGGL(relu_kernel<T>, dim3(grid_for(nvec)), dim3(256), 0, s, (const T*)x, nvec, (T*)out)
-  LPIPS_BY_DTYPE(CALL);
-#undef CALL
-  CHECK_LAUNCH();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(relu_kernel<T>, dim3(grid_for(nvec)), dim3(256), 0, s, (const T*)x, nvec, (T*)out);
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_maxpool2x2(int32_t dtype, const void* x, int64_t N, int32_t H, int32_t W, int32_t C, void* out, void* stream) {
   if (!x || !out || N <= 0 || H < 2 || W < 2 || C <= 0 || C % 8) return CVVAE_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const long long nvec = (long long)N * (H / 2) * (W / 2) * (C / 8);
-#define CALL(T) hipLaunchKernelGGL(maxpool2x2_kernel<T>, dim3(grid_for(nvec)), dim3(256), 0, s, (const T*)x, (long long)N, H, W, C, (T*)out)
-  LPIPS_BY_DTYPE(CALL);
-#undef CALL
-  CHECK_LAUNCH();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(maxpool2x2_kernel<T>, dim3(grid_for(nvec)), dim3(256), 0, s, (const T*)x, (long long)N, H, W, C, (T*)out);
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_relu_pool_bwd(int32_t dtype, const void* y, const void* g_tap, const void* g_pool, int64_t N, int32_t H, int32_t W,
@@ -368,12 +359,13 @@ int cvvae_relu_pool_bwd(int32_t dtype, const void* y, const void* g_tap, const v
   if (g_pool && (H < 2 || W < 2)) return CVVAE_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const long long nvec = (long long)N * ((H + 1) / 2) * ((W + 1) / 2) * (C / 8);
-#define CALL(T) \
-  hipLaunchKernelGGL(relu_pool_bwd_kernel<T>, dim3(grid_for(nvec)), dim3(256), 0, s, (const T*)y, (const T*)g_tap, (const T*)g_pool, \
-                     (long long)N, H, W, C, (T*)gx)
-  LPIPS_BY_DTYPE(CALL);
-#undef CALL
-  CHECK_LAUNCH();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(relu_pool_bwd_kernel<T>, dim3(grid_for(nvec)), dim3(256), 0, s, (const T*)y, (const T*)g_tap, (const T*)g_pool,
+                       (long long)N, H, W, C, (T*)gx);
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 size_t cvvae_lpips_head_workspace_bytes(int64_t N, int64_t HW, int32_t C) {
@@ -391,14 +383,15 @@ int cvvae_lpips_head(int32_t dtype, const void* f0, const void* f1, const float*
   const dim3 grid((unsigned)nblk, (unsigned)N);
 #define CALL_LP(T, LP) \
   hipLaunchKernelGGL((lpips_head_kernel<T, LP>), grid, dim3(256), 0, s, (const T*)f0, (const T*)f1, w, (long long)HW, (float*)workspace)
-#define CALL(T) \
-  if (lp == 8) CALL_LP(T, 8); else if (lp == 16) CALL_LP(T, 16); else if (lp == 32) CALL_LP(T, 32); else CALL_LP(T, 64)
-  LPIPS_BY_DTYPE(CALL);
-#undef CALL
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (lp == 8) CALL_LP(T, 8); else if (lp == 16) CALL_LP(T, 16); else if (lp == 32) CALL_LP(T, 32); else CALL_LP(T, 64);
+  });
 #undef CALL_LP
+  if (!ok) return CVVAE_EINVAL;
   hipLaunchKernelGGL(lpips_head_final_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s, (const float*)workspace, nblk,
                      (long long)N, 1.0f / (float)HW, out);
-  CHECK_LAUNCH();
+  return launch_status();
 }
 
 int cvvae_lpips_head_bwd(int32_t dtype, const void* f0, const void* f1, const float* w, const float* gout, int64_t N, int64_t HW,
@@ -411,12 +404,13 @@ int cvvae_lpips_head_bwd(int32_t dtype, const void* f0, const void* f1, const fl
 #define CALL_LP(T, LP) \
   hipLaunchKernelGGL((lpips_head_bwd_kernel<T, LP>), grid, dim3(256), 0, s, (const T*)f0, (const T*)f1, w, gout, (long long)HW, \
                      1.0f / (float)HW, (T*)g_f0, (T*)g_f1)
-#define CALL(T) \
-  if (lp == 8) CALL_LP(T, 8); else if (lp == 16) CALL_LP(T, 16); else if (lp == 32) CALL_LP(T, 32); else CALL_LP(T, 64)
-  LPIPS_BY_DTYPE(CALL);
-#undef CALL
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (lp == 8) CALL_LP(T, 8); else if (lp == 16) CALL_LP(T, 16); else if (lp == 32) CALL_LP(T, 32); else CALL_LP(T, 64);
+  });
 #undef CALL_LP
-  CHECK_LAUNCH();
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 }  // extern "C"

@@ -325,19 +325,6 @@ __global__ void pack_upfold_xp_kernel(const float* __restrict__ src, int Cout, i
 // SUB = channels per statistics slot of a lane's 8 channels: 4 (groups of whole quads), or 2 for groups of 2 or 6 channels
 // (GroupNorm(32, 64) of the discriminator) -- the same arithmetic on pairs.
 // ---------------------------------------------------------------------------------------------------------
-struct WStat {
-  float n, mean, m2;
-};
-__device__ __forceinline__ void chan_merge(WStat& a, const WStat& b) {
-  if (b.n == 0.f) return;
-  const float n = a.n + b.n;
-  const float d = b.mean - a.mean;
-  const float f = b.n / n;
-  a.mean += d * f;
-  a.m2 += b.m2 + d * d * a.n * f;
-  a.n = n;
-}
-
 template <typename T, int SUB = 4>
 __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x, long long S, int C, long long ps,
                                                          int G, int nsplit, float* __restrict__ ws) {
@@ -641,11 +628,6 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
 // Pass 1 (gn_bwd_reduce_kernel) writes, per (row, pixel split, group), sum(gh) and sum(gh * xh); pass 2 (gn_bwd_apply_kernel) sums
 // the splits in index order (deterministic) and applies.  Channel quads never straddle a group (C / G a multiple of 4).
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float silu_grad_f(float a) {
-  const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-a));
-  return sg * (1.0f + a * (1.0f - sg));
-}
-
 struct GnBwdTab {  // the per-channel tables of my 8 channels
   float rs[8], nm[8], ga[8], be[8];
 };
@@ -1343,8 +1325,6 @@ __global__ __launch_bounds__(256) void blend_kernel(const T* __restrict__ a, int
 
 using namespace cvvae;
 
-#define CHECK_LAUNCH() return (int)hipGetLastError()
-
 extern "C" {
 
 size_t cvvae_packed_weight_bytes(int32_t Cout, int32_t Cin, int32_t taps) {
@@ -1390,15 +1370,7 @@ static int pack_impl(int32_t dtype, const void* src, int32_t batch, int64_t s_ba
   const long long n = (long long)nb * nchunks * taps * ksub * 64;
   const int grid = (int)((n + 255) / 256);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CVVAE_BF16)
-    hipLaunchKernelGGL(pack_weights_kernel<__bf16>, dim3(grid, batch), dim3(256), 0, s, (const __bf16*)src, Cout_src, Cin_src,
-                       taps, (long long)s_co, (long long)s_ci, (long long)s_tap, nchunks, ksub, (__bf16*)dst, n, fold_n,
-                       (long long)s_fold, (long long)s_batch, (long long)(d_batch_bytes / 2), dst_taps, dst_tap0);
-  else if (dtype == CVVAE_F16)
-    hipLaunchKernelGGL(pack_weights_kernel<_Float16>, dim3(grid, batch), dim3(256), 0, s, (const _Float16*)src, Cout_src,
-                       Cin_src, taps, (long long)s_co, (long long)s_ci, (long long)s_tap, nchunks, ksub, (_Float16*)dst, n,
-                       fold_n, (long long)s_fold, (long long)s_batch, (long long)(d_batch_bytes / 2), dst_taps, dst_tap0);
-  else if (dtype == CVVAE_F32 || dtype == CVVAE_F32Q || dtype == CVVAE_F32Q6) {  // fp32 source -> split-precision records (3 per (k16, tap); one thread per record TRIPLE)
+  if (dtype == CVVAE_F32 || dtype == CVVAE_F32Q || dtype == CVVAE_F32Q6) {  // fp32 source -> split-precision records (3 per (k16, tap); one thread per record TRIPLE)
     // fast-fp32 pairs stay inside a run of kH*kW taps (the kernel walks 3-tap time kernels as time groups of kH*kW steps):
     // 27 / 54 (time-fold slots) / 9 -> runs of 9, 12 / 24 / 4 -> runs of 4 (the folded-upsample phases come through upfold_launch)
     int qrun = 0;
@@ -1409,10 +1381,16 @@ static int pack_impl(int32_t dtype, const void* src, int32_t batch, int64_t s_ba
     hipLaunchKernelGGL(pack_weights_xp_kernel, dim3(grid, batch), dim3(256), 0, s, (const float*)src, Cout_src, Cin_src, taps,
                        (long long)s_co, (long long)s_ci, (long long)s_tap, nchunks, (_Float16*)dst, n, fold_n, (long long)s_fold,
                        (long long)s_batch, (long long)(d_batch_bytes / 2), dst_taps, dst_tap0, qrun, dtype == CVVAE_F32Q6 ? 1 : 0);
+  } else {
+    const bool ok = by_dtype16(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(pack_weights_kernel<T>, dim3(grid, batch), dim3(256), 0, s, (const T*)src, Cout_src, Cin_src, taps,
+                         (long long)s_co, (long long)s_ci, (long long)s_tap, nchunks, ksub, (T*)dst, n, fold_n, (long long)s_fold,
+                         (long long)s_batch, (long long)(d_batch_bytes / 2), dst_taps, dst_tap0);
+    });
+    if (!ok) return CVVAE_EINVAL;
   }
-  else
-    return CVVAE_EINVAL;
-  CHECK_LAUNCH();
+  return launch_status();
 }
 
 // Time-fold slots.  A 3-tap time kernel at a clip boundary reads the SAME stored frame through two or three of its taps
@@ -1444,19 +1422,19 @@ static int upfold_launch(int32_t dtype, const void* src, int32_t Cout, int32_t C
   const long long stride = (long long)(cvvae_packed_weight_bytes(Cout, Cin_pad, dst_taps * (f32 ? 3 : 1)) / 2);
   const int grid = (int)((4 * per_phase + 255) / 256);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CVVAE_BF16)
-    hipLaunchKernelGGL(pack_upfold_kernel<__bf16>, dim3(grid), dim3(256), 0, s, (const __bf16*)src, Cout, Cin, nchunks,
-                       (__bf16*)dst, per_phase, stride, tfold, dst_taps, dst_tap0);
-  else if (dtype == CVVAE_F16)
-    hipLaunchKernelGGL(pack_upfold_kernel<_Float16>, dim3(grid), dim3(256), 0, s, (const _Float16*)src, Cout, Cin, nchunks,
-                       (_Float16*)dst, per_phase, stride, tfold, dst_taps, dst_tap0);
-  else if (f32)
+  if (f32) {
     hipLaunchKernelGGL(pack_upfold_xp_kernel, dim3(grid), dim3(256), 0, s, (const float*)src, Cout, Cin, nchunks, (_Float16*)dst,
                        per_phase, stride, tfold, dst_taps, dst_tap0, (dtype == CVVAE_F32Q || dtype == CVVAE_F32Q6) ? 4 : 0,
                        dtype == CVVAE_F32Q6 ? 1 : 0);
-  else
-    return CVVAE_EINVAL;
-  CHECK_LAUNCH();
+  } else {
+    const bool ok = by_dtype16(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(pack_upfold_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)src, Cout, Cin, nchunks, (T*)dst, per_phase,
+                         stride, tfold, dst_taps, dst_tap0);
+    });
+    if (!ok) return CVVAE_EINVAL;
+  }
+  return launch_status();
 }
 
 // the four folded 3x2x2 phase kernels of cvvae_pack_weights_upfold with the time-fold slots appended: 24 taps per phase
@@ -1495,27 +1473,19 @@ int cvvae_gn_stats(int32_t dtype, const void* x, int32_t rows, int64_t S, int32_
   const int nsplit = gn_nsplit(S);
   hipStream_t s = (hipStream_t)stream;
   const bool quads = (C / groups) % 4 == 0;  // else pairs: groups of 2 or 6 channels
-#define GN_PARTIAL(T) \
-  do { \
-    if (quads) \
-      hipLaunchKernelGGL((gn_partial_kernel<T, 4>), dim3(nsplit, rows), dim3(256), 0, s, (const T*)x, (long long)S, C, \
-                         (long long)pix_stride, groups, nsplit, (float*)workspace); \
-    else \
-      hipLaunchKernelGGL((gn_partial_kernel<T, 2>), dim3(nsplit, rows), dim3(256), 0, s, (const T*)x, (long long)S, C, \
-                         (long long)pix_stride, groups, nsplit, (float*)workspace); \
-  } while (0)
-  if (dtype == CVVAE_BF16)
-    GN_PARTIAL(__bf16);
-  else if (dtype == CVVAE_F16)
-    GN_PARTIAL(_Float16);
-  else if (dtype == CVVAE_F32)
-    GN_PARTIAL(float);
-  else
-    return CVVAE_EINVAL;
-#undef GN_PARTIAL
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (quads)
+      hipLaunchKernelGGL((gn_partial_kernel<T, 4>), dim3(nsplit, rows), dim3(256), 0, s, (const T*)x, (long long)S, C,
+                         (long long)pix_stride, groups, nsplit, (float*)workspace);
+    else
+      hipLaunchKernelGGL((gn_partial_kernel<T, 2>), dim3(nsplit, rows), dim3(256), 0, s, (const T*)x, (long long)S, C,
+                         (long long)pix_stride, groups, nsplit, (float*)workspace);
+  });
+  if (!ok) return CVVAE_EINVAL;
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(rows), dim3(256), 0, s, (const float*)workspace, nsplit, groups, C, eps, gamma,
                      beta, scale, shift);
-  CHECK_LAUNCH();
+  return launch_status();
 }
 
 int cvvae_gn_silu_apply(int32_t dtype, const void* x, int32_t rows, int64_t S, int32_t C, int64_t pix_stride,
@@ -1525,18 +1495,13 @@ int cvvae_gn_silu_apply(int32_t dtype, const void* x, int32_t rows, int64_t S, i
   long long blocks = (nvec + 255) / 256;
   if (blocks > 256LL * 64) blocks = 256LL * 64;  // grid-stride beyond 64 blocks per CU
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CVVAE_BF16)
-    hipLaunchKernelGGL(gn_silu_apply_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, s, (const __bf16*)x, (long long)S, C,
-                       (long long)pix_stride, scale, shift, silu, (__bf16*)out, nvec);
-  else if (dtype == CVVAE_F16)
-    hipLaunchKernelGGL(gn_silu_apply_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, s, (const _Float16*)x, (long long)S, C,
-                       (long long)pix_stride, scale, shift, silu, (_Float16*)out, nvec);
-  else if (dtype == CVVAE_F32)
-    hipLaunchKernelGGL(gn_silu_apply_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)x, (long long)S, C,
-                       (long long)pix_stride, scale, shift, silu, (float*)out, nvec);
-  else
-    return CVVAE_EINVAL;
-  CHECK_LAUNCH();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(gn_silu_apply_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, s, (const T*)x, (long long)S, C,
+                       (long long)pix_stride, scale, shift, silu, (T*)out, nvec);
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_gn_finalize(const float* partials, int32_t rows, int64_t slabs, int32_t C, int32_t groups, float eps,
@@ -1551,7 +1516,7 @@ int cvvae_gn_finalize_frames(const float* partials, int32_t rows, int32_t frames
     return CVVAE_EINVAL;
   hipLaunchKernelGGL(gn_finalize_slabs_kernel, dim3(groups, rows * frames), dim3(256), 0, (hipStream_t)stream, partials,
                      (long long)slabs, groups, C, eps, gamma, beta, scale, shift, frames);
-  CHECK_LAUNCH();
+  return launch_status();
 }
 
 int64_t cvvae_gn_bwd_workspace_bytes(int32_t rows, int32_t groups, int64_t S) {
@@ -1580,15 +1545,12 @@ int cvvae_gn_bwd_input_params(int32_t dtype, const void* x, const void* gy, cons
     return CVVAE_EINVAL;
   if (groups <= 0 || groups > 64 || C % groups || (C / groups) % 2 || C % 8 || C > 2048 || 256 % (C / 8)) return CVVAE_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CVVAE_BF16)
-    GN_BWD_LAUNCH(__bf16, dgamma, dbeta);
-  else if (dtype == CVVAE_F16)
-    GN_BWD_LAUNCH(_Float16, dgamma, dbeta);
-  else if (dtype == CVVAE_F32)
-    GN_BWD_LAUNCH(float, dgamma, dbeta);
-  else
-    return CVVAE_EINVAL;
-  CHECK_LAUNCH();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    GN_BWD_LAUNCH(T, dgamma, dbeta);
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_gn_bwd_input(int32_t dtype, const void* x, const void* gy, const void* add, int32_t rows, int64_t S, int32_t C,
@@ -1598,33 +1560,25 @@ int cvvae_gn_bwd_input(int32_t dtype, const void* x, const void* gy, const void*
   // 8-channel vectors that tile a 256-thread block; channel quads (or pairs) inside one group
   if (groups <= 0 || groups > 64 || C % groups || (C / groups) % 2 || C % 8 || C > 2048 || 256 % (C / 8)) return CVVAE_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CVVAE_BF16)
-    GN_BWD_LAUNCH(__bf16, nullptr, nullptr);
-  else if (dtype == CVVAE_F16)
-    GN_BWD_LAUNCH(_Float16, nullptr, nullptr);
-  else if (dtype == CVVAE_F32)
-    GN_BWD_LAUNCH(float, nullptr, nullptr);
-  else
-    return CVVAE_EINVAL;
-  CHECK_LAUNCH();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    GN_BWD_LAUNCH(T, nullptr, nullptr);
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_softmax_bwd_rows(int32_t dtype, const void* p, int64_t ld_p, const float* gp, int64_t ld_g, int64_t rows, int32_t n_valid,
                            float alpha, void* gs, int64_t ld_o, void* stream) {
   if (!p || !gp || !gs || rows <= 0 || n_valid <= 0 || ld_p < n_valid || ld_g < n_valid || ld_o < n_valid) return CVVAE_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CVVAE_BF16)
-    hipLaunchKernelGGL(softmax_bwd_rows_kernel<__bf16>, dim3((unsigned)rows), dim3(256), 0, s, (const __bf16*)p, (long long)ld_p, gp,
-                       (long long)ld_g, n_valid, alpha, (__bf16*)gs, (long long)ld_o);
-  else if (dtype == CVVAE_F16)
-    hipLaunchKernelGGL(softmax_bwd_rows_kernel<_Float16>, dim3((unsigned)rows), dim3(256), 0, s, (const _Float16*)p, (long long)ld_p,
-                       gp, (long long)ld_g, n_valid, alpha, (_Float16*)gs, (long long)ld_o);
-  else if (dtype == CVVAE_F32)
-    hipLaunchKernelGGL(softmax_bwd_rows_kernel<float>, dim3((unsigned)rows), dim3(256), 0, s, (const float*)p, (long long)ld_p, gp,
-                       (long long)ld_g, n_valid, alpha, (float*)gs, (long long)ld_o);
-  else
-    return CVVAE_EINVAL;
-  CHECK_LAUNCH();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(softmax_bwd_rows_kernel<T>, dim3((unsigned)rows), dim3(256), 0, s, (const T*)p, (long long)ld_p, gp,
+                       (long long)ld_g, n_valid, alpha, (T*)gs, (long long)ld_o);
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_upsample2x_sum(int32_t dtype, const void* g, int64_t N, int32_t H, int32_t W, int32_t C, void* out, void* stream) {
@@ -1632,18 +1586,12 @@ int cvvae_upsample2x_sum(int32_t dtype, const void* g, int64_t N, int32_t H, int
   long long blocks = ((long long)N * H * W * (C / 8) + 255) / 256;
   if (blocks > 256LL * 64) blocks = 256LL * 64;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CVVAE_BF16)
-    hipLaunchKernelGGL(upsample2x_sum_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, s, (const __bf16*)g, (long long)N, H, W, C,
-                       (__bf16*)out);
-  else if (dtype == CVVAE_F16)
-    hipLaunchKernelGGL(upsample2x_sum_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, s, (const _Float16*)g, (long long)N, H, W,
-                       C, (_Float16*)out);
-  else if (dtype == CVVAE_F32)
-    hipLaunchKernelGGL(upsample2x_sum_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)g, (long long)N, H, W, C,
-                       (float*)out);
-  else
-    return CVVAE_EINVAL;
-  CHECK_LAUNCH();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(upsample2x_sum_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, s, (const T*)g, (long long)N, H, W, C, (T*)out);
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_layernorm(int32_t dtype, const void* x, int64_t P, int32_t C, float eps, const float* gamma, const float* beta,
@@ -1651,36 +1599,24 @@ int cvvae_layernorm(int32_t dtype, const void* x, int64_t P, int32_t C, float ep
   if (!x || !out || !gamma || !beta || P <= 0 || C <= 0 || C % 8) return CVVAE_EINVAL;
   const int grid = (int)((P + 3) / 4);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CVVAE_BF16)
-    hipLaunchKernelGGL(layernorm_kernel<__bf16>, dim3(grid), dim3(256), 0, s, (const __bf16*)x, (long long)P, C, eps, gamma,
-                       beta, (__bf16*)out);
-  else if (dtype == CVVAE_F16)
-    hipLaunchKernelGGL(layernorm_kernel<_Float16>, dim3(grid), dim3(256), 0, s, (const _Float16*)x, (long long)P, C, eps,
-                       gamma, beta, (_Float16*)out);
-  else if (dtype == CVVAE_F32)
-    hipLaunchKernelGGL(layernorm_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)x, (long long)P, C, eps,
-                       gamma, beta, (float*)out);
-  else
-    return CVVAE_EINVAL;
-  CHECK_LAUNCH();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(layernorm_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)x, (long long)P, C, eps, gamma, beta, (T*)out);
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_softmax_rows(int32_t dtype, const float* sc, int64_t rows, int32_t n_valid, int64_t ld_s, void* p, int64_t ld_p,
                        void* stream) {
   if (!sc || !p || rows <= 0 || n_valid <= 0 || ld_s < n_valid || ld_p < n_valid) return CVVAE_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CVVAE_BF16)
-    hipLaunchKernelGGL(softmax_rows_kernel<__bf16>, dim3((unsigned)rows), dim3(256), 0, s, sc, n_valid, (long long)ld_s,
-                       (__bf16*)p, (long long)ld_p);
-  else if (dtype == CVVAE_F16)
-    hipLaunchKernelGGL(softmax_rows_kernel<_Float16>, dim3((unsigned)rows), dim3(256), 0, s, sc, n_valid, (long long)ld_s,
-                       (_Float16*)p, (long long)ld_p);
-  else if (dtype == CVVAE_F32)
-    hipLaunchKernelGGL(softmax_rows_kernel<float>, dim3((unsigned)rows), dim3(256), 0, s, sc, n_valid, (long long)ld_s,
-                       (float*)p, (long long)ld_p);
-  else
-    return CVVAE_EINVAL;
-  CHECK_LAUNCH();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(softmax_rows_kernel<T>, dim3((unsigned)rows), dim3(256), 0, s, sc, n_valid, (long long)ld_s, (T*)p, (long long)ld_p);
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_transpose(int32_t dtype, const void* in, int32_t batch, int32_t R, int32_t C, int64_t ld_in, int64_t bs_in,
@@ -1696,7 +1632,7 @@ int cvvae_transpose(int32_t dtype, const void* in, int32_t batch, int32_t R, int
                        (long long)bs_out);
   else
     return CVVAE_EINVAL;
-  CHECK_LAUNCH();
+  return launch_status();
 }
 
 int cvvae_temporal_attention(int32_t dtype, const void* q, const void* k, const void* v, int32_t B, int32_t T, int64_t S,
@@ -1708,32 +1644,22 @@ int cvvae_temporal_attention(int32_t dtype, const void* q, const void* k, const 
   if (T > 8) {  // general frame count: one wave per (pixel, query frame)
     if (C > 2048 || P * T >= (1LL << 33)) return CVVAE_EUNSUPPORTED;
     const int gridg = (int)((P * T + 3) / 4);
-    if (dtype == CVVAE_BF16)
-      hipLaunchKernelGGL(temporal_attn_general_kernel<__bf16>, dim3(gridg), dim3(256), 0, s, (const __bf16*)q, (const __bf16*)k,
-                         (const __bf16*)v, P, T, (long long)S, C, scale, (__bf16*)out);
-    else if (dtype == CVVAE_F16)
-      hipLaunchKernelGGL(temporal_attn_general_kernel<_Float16>, dim3(gridg), dim3(256), 0, s, (const _Float16*)q,
-                         (const _Float16*)k, (const _Float16*)v, P, T, (long long)S, C, scale, (_Float16*)out);
-    else if (dtype == CVVAE_F32)
-      hipLaunchKernelGGL(temporal_attn_general_kernel<float>, dim3(gridg), dim3(256), 0, s, (const float*)q,
-                         (const float*)k, (const float*)v, P, T, (long long)S, C, scale, (float*)out);
-    else
-      return CVVAE_EINVAL;
-    CHECK_LAUNCH();
+    const bool ok = by_dtype(dtype, [&](auto tag) {
+      using E = typename decltype(tag)::type;  // (T is the frame count here)
+      hipLaunchKernelGGL(temporal_attn_general_kernel<E>, dim3(gridg), dim3(256), 0, s, (const E*)q, (const E*)k, (const E*)v, P, T,
+                         (long long)S, C, scale, (E*)out);
+    });
+    if (!ok) return CVVAE_EINVAL;
+    return launch_status();
   }
   const int grid = (int)((P + 3) / 4);
-  if (dtype == CVVAE_BF16)
-    hipLaunchKernelGGL(temporal_attn_kernel<__bf16>, dim3(grid), dim3(256), 0, s, (const __bf16*)q, (const __bf16*)k,
-                       (const __bf16*)v, P, T, (long long)S, C, scale, (__bf16*)out);
-  else if (dtype == CVVAE_F16)
-    hipLaunchKernelGGL(temporal_attn_kernel<_Float16>, dim3(grid), dim3(256), 0, s, (const _Float16*)q, (const _Float16*)k,
-                       (const _Float16*)v, P, T, (long long)S, C, scale, (_Float16*)out);
-  else if (dtype == CVVAE_F32)
-    hipLaunchKernelGGL(temporal_attn_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)q, (const float*)k,
-                       (const float*)v, P, T, (long long)S, C, scale, (float*)out);
-  else
-    return CVVAE_EINVAL;
-  CHECK_LAUNCH();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using E = typename decltype(tag)::type;
+    hipLaunchKernelGGL(temporal_attn_kernel<E>, dim3(grid), dim3(256), 0, s, (const E*)q, (const E*)k, (const E*)v, P, T, (long long)S,
+                       C, scale, (E*)out);
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_ncdhw_to_ndhwc(int32_t src_dtype, int32_t dst_dtype, const void* in, int32_t B, int32_t C, int32_t T, int32_t H,
@@ -1742,27 +1668,16 @@ int cvvae_ncdhw_to_ndhwc(int32_t src_dtype, int32_t dst_dtype, const void* in, i
   const long long THW = (long long)T * H * W, npix = THW * B;
   const int grid = (int)((npix + 255) / 256);
   hipStream_t s = (hipStream_t)stream;
-#define L(TS, TD) \
-  hipLaunchKernelGGL((ncdhw_to_ndhwc_kernel<TS, TD>), dim3(grid), dim3(256), 0, s, (const TS*)in, C, THW, Cpad, npix, (TD*)out)
-  if (dst_dtype == CVVAE_BF16) {
-    if (src_dtype == CVVAE_BF16) L(__bf16, __bf16);
-    else if (src_dtype == CVVAE_F16) L(_Float16, __bf16);
-    else if (src_dtype == 2) L(float, __bf16);
-    else return CVVAE_EINVAL;
-  } else if (dst_dtype == CVVAE_F16) {
-    if (src_dtype == CVVAE_BF16) L(__bf16, _Float16);
-    else if (src_dtype == CVVAE_F16) L(_Float16, _Float16);
-    else if (src_dtype == 2) L(float, _Float16);
-    else return CVVAE_EINVAL;
-  } else if (dst_dtype == CVVAE_F32) {
-    if (src_dtype == CVVAE_BF16) L(__bf16, float);
-    else if (src_dtype == CVVAE_F16) L(_Float16, float);
-    else if (src_dtype == 2) L(float, float);
-    else return CVVAE_EINVAL;
-  } else
-    return CVVAE_EINVAL;
-#undef L
-  CHECK_LAUNCH();
+  bool ok = false;
+  by_dtype(dst_dtype, [&](auto td) {
+    ok = by_dtype(src_dtype, [&](auto ts) {
+      using TS = typename decltype(ts)::type;
+      using TD = typename decltype(td)::type;
+      hipLaunchKernelGGL((ncdhw_to_ndhwc_kernel<TS, TD>), dim3(grid), dim3(256), 0, s, (const TS*)in, C, THW, Cpad, npix, (TD*)out);
+    });
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_ncdhw_to_rowpack(int32_t src_dtype, int32_t dst_dtype, const void* in, int32_t B, int32_t C, int32_t T, int32_t H,
@@ -1775,22 +1690,18 @@ int cvvae_ncdhw_to_rowpack(int32_t src_dtype, int32_t dst_dtype, const void* in,
   const size_t es = dst_dtype == CVVAE_F32 ? 4 : 2;
   hipError_t me = hipMemsetAsync((char*)out + (size_t)npo * 4 * es, 0, 16 * es, s);
   if (me != hipSuccess) return (int)me;
-#define L(TS, TD) \
-  hipLaunchKernelGGL((ncdhw_to_rowpack_kernel<TS, TD>), dim3(grid), dim3(256), 0, s, (const TS*)in, C, THW, W, pad_mode_w, npo, (TD*)out)
-  if (dst_dtype == CVVAE_BF16) {
-    if (src_dtype == CVVAE_BF16) L(__bf16, __bf16);
-    else if (src_dtype == CVVAE_F16) L(_Float16, __bf16);
-    else if (src_dtype == CVVAE_F32) L(float, __bf16);
-    else return CVVAE_EINVAL;
-  } else if (dst_dtype == CVVAE_F16) {
-    if (src_dtype == CVVAE_BF16) L(__bf16, _Float16);
-    else if (src_dtype == CVVAE_F16) L(_Float16, _Float16);
-    else if (src_dtype == CVVAE_F32) L(float, _Float16);
-    else return CVVAE_EINVAL;
-  } else
-    return CVVAE_EUNSUPPORTED;  // (fp32 models keep the channel-padded first layer: no split-precision (3,3,1) instance)
-#undef L
-  CHECK_LAUNCH();
+  bool src_ok = false;
+  const bool dst_ok = by_dtype16(dst_dtype, [&](auto td) {
+    src_ok = by_dtype(src_dtype, [&](auto ts) {
+      using TS = typename decltype(ts)::type;
+      using TD = typename decltype(td)::type;
+      hipLaunchKernelGGL((ncdhw_to_rowpack_kernel<TS, TD>), dim3(grid), dim3(256), 0, s, (const TS*)in, C, THW, W, pad_mode_w, npo,
+                         (TD*)out);
+    });
+  });
+  if (!dst_ok) return CVVAE_EUNSUPPORTED;  // (fp32 models keep the channel-padded first layer: no split-precision (3,3,1) instance)
+  if (!src_ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_ndhwc_to_rowpack(int32_t dtype, const void* in, int32_t B, int32_t C, int32_t T, int32_t H, int32_t W, int64_t pix_stride,
@@ -1803,13 +1714,12 @@ int cvvae_ndhwc_to_rowpack(int32_t dtype, const void* in, int32_t B, int32_t C, 
   hipStream_t s = (hipStream_t)stream;
   hipError_t me = hipMemsetAsync((char*)out + (size_t)npo * 4 * 2, 0, 16 * 2, s);
   if (me != hipSuccess) return (int)me;
-  if (dtype == CVVAE_BF16)
-    hipLaunchKernelGGL(ndhwc_to_rowpack_kernel<__bf16>, dim3(grid), dim3(256), 0, s, (const __bf16*)in, C, (long long)pix_stride, W,
-                       pad_mode_w, npo, (__bf16*)out);
-  else
-    hipLaunchKernelGGL(ndhwc_to_rowpack_kernel<_Float16>, dim3(grid), dim3(256), 0, s, (const _Float16*)in, C, (long long)pix_stride, W,
-                       pad_mode_w, npo, (_Float16*)out);
-  CHECK_LAUNCH();
+  by_dtype16(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(ndhwc_to_rowpack_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)in, C, (long long)pix_stride, W, pad_mode_w,
+                       npo, (T*)out);
+  });
+  return launch_status();
 }
 
 int cvvae_ndhwc_to_ncdhw(int32_t dtype, const void* in, int32_t B, int32_t C, int32_t T, int32_t H, int32_t W,
@@ -1818,52 +1728,36 @@ int cvvae_ndhwc_to_ncdhw(int32_t dtype, const void* in, int32_t B, int32_t C, in
   const long long THW = (long long)T * H * W, npix = THW * B;
   const int grid = (int)((npix + 255) / 256);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CVVAE_BF16)
-    hipLaunchKernelGGL(ndhwc_to_ncdhw_kernel<__bf16>, dim3(grid), dim3(256), 0, s, (const __bf16*)in, C, THW,
-                       (long long)pix_stride, npix, (__bf16*)out);
-  else if (dtype == CVVAE_F16)
-    hipLaunchKernelGGL(ndhwc_to_ncdhw_kernel<_Float16>, dim3(grid), dim3(256), 0, s, (const _Float16*)in, C, THW,
-                       (long long)pix_stride, npix, (_Float16*)out);
-  else if (dtype == CVVAE_F32)
-    hipLaunchKernelGGL(ndhwc_to_ncdhw_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)in, C, THW,
-                       (long long)pix_stride, npix, (float*)out);
-  else
-    return CVVAE_EINVAL;
-  CHECK_LAUNCH();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(ndhwc_to_ncdhw_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)in, C, THW, (long long)pix_stride, npix, (T*)out);
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_frames_u8_to_ndhwc(int32_t dtype, const uint8_t* frames, int64_t npix, int32_t Cpad, void* out, void* stream) {
   if (!frames || !out || npix <= 0 || Cpad < 8 || Cpad % 8) return CVVAE_EINVAL;
   const int grid = (int)((npix + 255) / 256);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CVVAE_BF16)
-    hipLaunchKernelGGL(frames_u8_to_ndhwc_kernel<__bf16>, dim3(grid), dim3(256), 0, s, frames, (long long)npix, Cpad, (__bf16*)out);
-  else if (dtype == CVVAE_F16)
-    hipLaunchKernelGGL(frames_u8_to_ndhwc_kernel<_Float16>, dim3(grid), dim3(256), 0, s, frames, (long long)npix, Cpad,
-                       (_Float16*)out);
-  else if (dtype == CVVAE_F32)
-    hipLaunchKernelGGL(frames_u8_to_ndhwc_kernel<float>, dim3(grid), dim3(256), 0, s, frames, (long long)npix, Cpad,
-                       (float*)out);
-  else
-    return CVVAE_EINVAL;
-  CHECK_LAUNCH();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(frames_u8_to_ndhwc_kernel<T>, dim3(grid), dim3(256), 0, s, frames, (long long)npix, Cpad, (T*)out);
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_ncdhw_to_frames_u8(int32_t dtype, const void* in, int64_t thw, uint8_t* frames, void* stream) {
   if (!in || !frames || thw <= 0) return CVVAE_EINVAL;
   const int grid = (int)((thw + 255) / 256);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CVVAE_BF16)
-    hipLaunchKernelGGL(ncdhw_to_frames_u8_kernel<__bf16>, dim3(grid), dim3(256), 0, s, (const __bf16*)in, (long long)thw, frames);
-  else if (dtype == CVVAE_F16)
-    hipLaunchKernelGGL(ncdhw_to_frames_u8_kernel<_Float16>, dim3(grid), dim3(256), 0, s, (const _Float16*)in, (long long)thw,
-                       frames);
-  else if (dtype == CVVAE_F32)
-    hipLaunchKernelGGL(ncdhw_to_frames_u8_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)in, (long long)thw,
-                       frames);
-  else
-    return CVVAE_EINVAL;
-  CHECK_LAUNCH();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(ncdhw_to_frames_u8_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)in, (long long)thw, frames);
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_resize_u8_axis(const uint8_t* in, uint8_t* out, int64_t outer, int32_t in_size, int32_t out_size, int64_t inner,
@@ -1875,7 +1769,7 @@ int cvvae_resize_u8_axis(const uint8_t* in, uint8_t* out, int64_t outer, int32_t
   if (n >= (1LL << 31) * 256) return CVVAE_EUNSUPPORTED;
   hipLaunchKernelGGL(resize_u8_axis_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, out, n, in_size, out_size,
                      (long long)inner, xmin, xsize, w, ksize, precision);
-  CHECK_LAUNCH();
+  return launch_status();
 }
 
 int cvvae_conv_out_gather(int32_t dtype, const float* V, int32_t B, int32_t T, int32_t H, int32_t W, int32_t Cout, int64_t ldv,
@@ -1890,18 +1784,13 @@ int cvvae_conv_out_gather(int32_t dtype, const float* V, int32_t B, int32_t T, i
   if (nblk >= (1LL << 31)) return CVVAE_EUNSUPPORTED;
   const int grid = (int)nblk;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CVVAE_BF16)
-    hipLaunchKernelGGL((conv_out_gather_kernel<__bf16, 3>), dim3(grid), dim3(256), 0, s, V, T, H, W, (long long)ldv, bias, pad_mode_hw,
-                       npix, (__bf16*)out_ncdhw, out_u8);
-  else if (dtype == CVVAE_F16)
-    hipLaunchKernelGGL((conv_out_gather_kernel<_Float16, 3>), dim3(grid), dim3(256), 0, s, V, T, H, W, (long long)ldv, bias, pad_mode_hw,
-                       npix, (_Float16*)out_ncdhw, out_u8);
-  else if (dtype == CVVAE_F32)
-    hipLaunchKernelGGL((conv_out_gather_kernel<float, 3>), dim3(grid), dim3(256), 0, s, V, T, H, W, (long long)ldv, bias, pad_mode_hw,
-                       npix, (float*)out_ncdhw, out_u8);
-  else
-    return CVVAE_EUNSUPPORTED;
-  CHECK_LAUNCH();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using E = typename decltype(tag)::type;
+    hipLaunchKernelGGL((conv_out_gather_kernel<E, 3>), dim3(grid), dim3(256), 0, s, V, T, H, W, (long long)ldv, bias, pad_mode_hw,
+                       npix, (E*)out_ncdhw, out_u8);
+  });
+  if (!ok) return CVVAE_EUNSUPPORTED;
+  return launch_status();
 }
 
 int cvvae_blend(int32_t dtype, const void* a, int32_t Ha, int32_t Wa, void* b, int32_t Hb, int32_t Wb, int64_t rows,
@@ -1912,18 +1801,12 @@ int cvvae_blend(int32_t dtype, const void* a, int32_t Ha, int32_t Wa, void* b, i
   const long long n = rows * (axis == 0 ? (long long)overlap * Wb : (long long)Hb * overlap);
   const int grid = (int)((n + 255) / 256);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CVVAE_BF16)
-    hipLaunchKernelGGL(blend_kernel<__bf16>, dim3(grid), dim3(256), 0, s, (const __bf16*)a, Ha, Wa, (__bf16*)b, Hb, Wb,
-                       (long long)rows, overlap, axis);
-  else if (dtype == CVVAE_F16)
-    hipLaunchKernelGGL(blend_kernel<_Float16>, dim3(grid), dim3(256), 0, s, (const _Float16*)a, Ha, Wa, (_Float16*)b, Hb, Wb,
-                       (long long)rows, overlap, axis);
-  else if (dtype == CVVAE_F32)
-    hipLaunchKernelGGL(blend_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)a, Ha, Wa, (float*)b, Hb, Wb,
-                       (long long)rows, overlap, axis);
-  else
-    return CVVAE_EINVAL;
-  CHECK_LAUNCH();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(blend_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)a, Ha, Wa, (T*)b, Hb, Wb, (long long)rows, overlap, axis);
+  });
+  if (!ok) return CVVAE_EINVAL;
+  return launch_status();
 }
 
 int cvvae_abi_version(void) { return CVVAE_ABI_VERSION; }

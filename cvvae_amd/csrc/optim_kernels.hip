@@ -13,10 +13,7 @@
 // workgroup) merges the partials, thread t taking t, t + 256, ... serially, then the same workgroup sum.  Nothing is atomic and the
 // grid does not enter: the norm is a function of the values and the list order alone, bit-identical from run to run.
 // Longest chain of additions: 8 (CHUNK / 2048 = 4 groups: 7 + 1 each, 32) + 6 + 3 in a chunk, ceil(n_chunks / 256) + 6 + 3 in stage 2.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/cvvae.h"
+#include "pass_common.h"
 
 namespace cvvae {
 namespace optim {
@@ -28,42 +25,6 @@ constexpr int CHUNK = CVVAE_MT_CHUNK;
 constexpr int MAX_BLOCKS = 2048;     // grid cap (8 workgroups per CU), as loss_kernels.hip
 static_assert(CHUNK % TILE == 0, "a chunk is a whole number of tiles");
 
-__device__ __forceinline__ bool aligned16(const float* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// the n (<= 8) elements at p; the rest are zero
-__device__ __forceinline__ void load8(const float* p, int n, float (&f)[VEC]) {
-  if (n == VEC && aligned16(p)) {
-    const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) f[k] = (k < n) ? p[k] : 0.f;
-  }
-}
-
-__device__ __forceinline__ void store8(float* p, int n, const float (&f)[VEC]) {
-  if (n == VEC && aligned16(p)) {
-    reinterpret_cast<float4*>(p)[0] = make_float4(f[0], f[1], f[2], f[3]);
-    reinterpret_cast<float4*>(p)[1] = make_float4(f[4], f[5], f[6], f[7]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < VEC; ++k)
-      if (k < n) p[k] = f[k];
-  }
-}
-
-// workgroup sum in a fixed order, valid in thread 0; the trailing barrier frees the LDS slots for the next call
-__device__ __forceinline__ float block_sum(float x) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) x += __shfl_xor(x, m, 64);
-  __shared__ float sh[WG / 64];
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-  __syncthreads();
-  const float s = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-  __syncthreads();
-  return s;
-}
-
 __global__ __launch_bounds__(WG) void sumsq_kernel(const cvvae_mt_chunk* __restrict__ chunks, const cvvae_mt_tensor* __restrict__ tensors,
                                                    long long n_chunks, float* __restrict__ ws) {
   for (long long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
@@ -73,13 +34,14 @@ __global__ __launch_bounds__(WG) void sumsq_kernel(const cvvae_mt_chunk* __restr
     for (int i = threadIdx.x * VEC; i < ch.n; i += TILE) {
       const int n = (ch.n - i) < VEC ? (ch.n - i) : VEC;
       float f[VEC];
-      load8(g + i, n, f);
+      ld8_n(g + i, n, f);
       float s = 0.f;
 #pragma unroll
       for (int k = 0; k < VEC; ++k) s += f[k] * f[k];
       acc += s;
     }
     acc = block_sum(acc);
+    __syncthreads();  // frees block_sum's LDS slots for the next chunk
     if (threadIdx.x == 0) ws[c] = acc;
   }
 }
@@ -91,6 +53,7 @@ __global__ __launch_bounds__(WG) void norm_final_kernel(const float* __restrict_
   float acc = 0.f;
   for (long long i = threadIdx.x; i < n_chunks; i += WG) acc += ws[i];
   acc = block_sum(acc);
+  __syncthreads();  // as in sumsq_kernel; a single sum does not need it, it only keeps this kernel's code what it has been
   if (threadIdx.x == 0) {
     const float norm = sqrtf(acc);
     const float c = max_norm / (norm + 1e-6f);
@@ -108,10 +71,10 @@ __global__ __launch_bounds__(WG) void scale_kernel(const cvvae_mt_chunk* __restr
     for (int i = threadIdx.x * VEC; i < ch.n; i += TILE) {
       const int n = (ch.n - i) < VEC ? (ch.n - i) : VEC;
       float f[VEC];
-      load8(g + i, n, f);
+      ld8_n(g + i, n, f);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) f[k] = coef * f[k];
-      store8(g + i, n, f);
+      st8_n(g + i, f, n);
     }
   }
 }
@@ -133,10 +96,10 @@ __global__ __launch_bounds__(WG) void adamw_kernel(const cvvae_mt_chunk* __restr
     for (int i = threadIdx.x * VEC; i < ch.n; i += TILE) {
       const int n = (ch.n - i) < VEC ? (ch.n - i) : VEC;
       float fg[VEC], fp[VEC], fm[VEC], fv[VEC];
-      load8(g + i, n, fg);
-      load8(p + i, n, fp);
-      load8(m + i, n, fm);
-      load8(v + i, n, fv);
+      ld8_n(g + i, n, fg);
+      ld8_n(p + i, n, fp);
+      ld8_n(m + i, n, fm);
+      ld8_n(v + i, n, fv);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
         const float G = coef_dev ? coef * fg[k] : fg[k];
@@ -145,9 +108,9 @@ __global__ __launch_bounds__(WG) void adamw_kernel(const cvvae_mt_chunk* __restr
         const float denom = sqrtf(fv[k]) / t.bias2_sqrt + h.eps;
         fp[k] = fp[k] * h.decay - t.step_size * (fm[k] / denom);
       }
-      store8(p + i, n, fp);
-      store8(m + i, n, fm);
-      store8(v + i, n, fv);
+      st8_n(p + i, fp, n);
+      st8_n(m + i, fm, n);
+      st8_n(v + i, fv, n);
     }
   }
 }
@@ -162,11 +125,11 @@ __global__ __launch_bounds__(WG) void ema_kernel(const cvvae_mt_chunk* __restric
     for (int i = threadIdx.x * VEC; i < ch.n; i += TILE) {
       const int n = (ch.n - i) < VEC ? (ch.n - i) : VEC;
       float fp[VEC], fs[VEC];
-      load8(p + i, n, fp);
-      load8(s + i, n, fs);
+      ld8_n(p + i, n, fp);
+      ld8_n(s + i, n, fs);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) fs[k] = fs[k] - one_minus_decay * (fs[k] - fp[k]);
-      store8(s + i, n, fs);
+      st8_n(s + i, fs, n);
     }
   }
 }
@@ -185,6 +148,7 @@ static inline int check_list(int32_t dtype, const void* chunks, const void* tens
 }  // namespace optim
 }  // namespace cvvae
 
+using namespace cvvae;
 using namespace cvvae::optim;
 
 extern "C" {
@@ -203,7 +167,7 @@ int cvvae_mt_grad_norm(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_
   if (rc == 0)
     hipLaunchKernelGGL(sumsq_kernel, dim3(blocks_for(n_chunks)), dim3(WG), 0, s, chunks, tensors, (long long)n_chunks, (float*)workspace);
   hipLaunchKernelGGL(norm_final_kernel, dim3(1), dim3(WG), 0, s, (const float*)workspace, (long long)n_chunks, max_norm, out2);
-  return (int)hipGetLastError();
+  return launch_status();
 }
 
 int cvvae_mt_scale(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, const float* coef_dev,
@@ -213,7 +177,7 @@ int cvvae_mt_scale(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_t
   if (rc != 0) return rc < 0 ? rc : CVVAE_OK;
   hipLaunchKernelGGL(scale_kernel, dim3(blocks_for(n_chunks)), dim3(WG), 0, (hipStream_t)stream, chunks, tensors, (long long)n_chunks,
                      coef_dev);
-  return (int)hipGetLastError();
+  return launch_status();
 }
 
 int cvvae_mt_adamw(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, double lr, double beta1,
@@ -225,7 +189,7 @@ int cvvae_mt_adamw(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_t
   const AdamW h{(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)(1.0 - lr * weight_decay)};
   hipLaunchKernelGGL(adamw_kernel, dim3(blocks_for(n_chunks)), dim3(WG), 0, (hipStream_t)stream, chunks, tensors, (long long)n_chunks, h,
                      coef_dev);
-  return (int)hipGetLastError();
+  return launch_status();
 }
 
 int cvvae_mt_ema(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float one_minus_decay,
@@ -234,7 +198,7 @@ int cvvae_mt_ema(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_ten
   if (rc != 0) return rc < 0 ? rc : CVVAE_OK;
   hipLaunchKernelGGL(ema_kernel, dim3(blocks_for(n_chunks)), dim3(WG), 0, (hipStream_t)stream, chunks, tensors, (long long)n_chunks,
                      one_minus_decay);
-  return (int)hipGetLastError();
+  return launch_status();
 }
 
 }  // extern "C"

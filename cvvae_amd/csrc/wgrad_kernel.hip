@@ -770,11 +770,6 @@ static int wgrad_launch(const cvvae_conv_desc* d, const void* a, const void* gy,
 //   d beta[c] = sum g * act'(a),  d gamma[c] = sum g * act'(a) * xh      (xh, a as in gn_bwd_*: misc_kernels.hip)
 // Two passes: per (row, split) partial sums [C][2] written in place, then summed in index order.
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float silu_grad2_f(float a) {
-  const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-a));
-  return sg * (1.0f + a * (1.0f - sg));
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void chan_sums_kernel(const T* __restrict__ x, const T* __restrict__ g, long long S, int C,
                                                         long long g_ps, int nsplit, const float* __restrict__ rs,
@@ -823,7 +818,7 @@ __global__ __launch_bounds__(256) void chan_sums_kernel(const T* __restrict__ x,
           for (int j = 0; j < 8; ++j) {
             const float xh = __builtin_fmaf(f[u][j], trs[j], tnm[j]);
             const float a = __builtin_fmaf(xh, tga[j], tbe[j]);
-            const float ga = gg[u][j] * (silu ? silu_grad2_f(a) : 1.0f);
+            const float ga = gg[u][j] * (silu ? silu_grad_f(a) : 1.0f);
             s1[j] += ga;
             s2[j] += ga * xh;
           }
@@ -1122,21 +1117,16 @@ int cvvae_conv_wgrad_bias(const cvvae_conv_desc* d, const void* a, const void* g
   if (!(d->kH == d->kW && (d->kH == 3 || d->kH == 1) && (d->kT == 3 || d->kT == 1))) return CVVAE_EUNSUPPORTED;
   if (d->sT < 1 || d->sT > 2 || d->sH < 1 || d->sH > 2 || d->sW < 1 || d->sW > 2 || d->sH != d->sW) return CVVAE_EUNSUPPORTED;
   const bool k3 = d->kH == 3;
-  switch (d->dtype) {
-    case CVVAE_BF16:
-      return k3 ? wgrad_launch<__bf16, 3, false>(d, a, gy, gy_pix_stride, dw, dbias, workspace, stream)
-                : wgrad_launch<__bf16, 1, false>(d, a, gy, gy_pix_stride, dw, dbias, workspace, stream);
-    case CVVAE_F16:
-      return k3 ? wgrad_launch<_Float16, 3, false>(d, a, gy, gy_pix_stride, dw, dbias, workspace, stream)
-                : wgrad_launch<_Float16, 1, false>(d, a, gy, gy_pix_stride, dw, dbias, workspace, stream);
-    case CVVAE_F32:
-    case CVVAE_F32Q:
-    case CVVAE_F32Q6:
-      return k3 ? wgrad_launch<__bf16, 3, true>(d, a, gy, gy_pix_stride, dw, dbias, workspace, stream)
-                : wgrad_launch<__bf16, 1, true>(d, a, gy, gy_pix_stride, dw, dbias, workspace, stream);
-    default:
-      return CVVAE_EINVAL;
-  }
+  if (d->dtype == CVVAE_F32 || d->dtype == CVVAE_F32Q || d->dtype == CVVAE_F32Q6)
+    return k3 ? wgrad_launch<__bf16, 3, true>(d, a, gy, gy_pix_stride, dw, dbias, workspace, stream)
+              : wgrad_launch<__bf16, 1, true>(d, a, gy, gy_pix_stride, dw, dbias, workspace, stream);
+  int rc = CVVAE_EINVAL;
+  by_dtype16(d->dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    rc = k3 ? wgrad_launch<T, 3, false>(d, a, gy, gy_pix_stride, dw, dbias, workspace, stream)
+            : wgrad_launch<T, 1, false>(d, a, gy, gy_pix_stride, dw, dbias, workspace, stream);
+  });
+  return rc;
 }
 
 int64_t cvvae_channel_sums_workspace_bytes(int32_t rows, int64_t S, int32_t C) {
@@ -1156,23 +1146,13 @@ int cvvae_channel_sums(int32_t dtype, const void* x, const void* g, int64_t g_pi
   if ((C >> 3) > 256) return CVVAE_EUNSUPPORTED;
   const int nsplit = chan_sums_splits(S, rows, C);
   float* ws = (float*)workspace;
-  switch (dtype) {
-    case CVVAE_BF16:
-      hipLaunchKernelGGL(chan_sums_kernel<__bf16>, dim3(nsplit, rows), dim3(256), 0, stream, (const __bf16*)x, (const __bf16*)g, S, C,
-                         g_pix_stride, nsplit, rstd, nmean, gamma, beta, silu, ws);
-      break;
-    case CVVAE_F16:
-      hipLaunchKernelGGL(chan_sums_kernel<_Float16>, dim3(nsplit, rows), dim3(256), 0, stream, (const _Float16*)x, (const _Float16*)g,
-                         S, C, g_pix_stride, nsplit, rstd, nmean, gamma, beta, silu, ws);
-      break;
-    case CVVAE_F32:
-      hipLaunchKernelGGL(chan_sums_kernel<float>, dim3(nsplit, rows), dim3(256), 0, stream, (const float*)x, (const float*)g, S, C,
-                         g_pix_stride, nsplit, rstd, nmean, gamma, beta, silu, ws);
-      break;
-    default:
-      return CVVAE_EINVAL;
-  }
-  int rc = (int)hipGetLastError();
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(chan_sums_kernel<T>, dim3(nsplit, rows), dim3(256), 0, stream, (const T*)x, (const T*)g, S, C, g_pix_stride, nsplit,
+                       rstd, nmean, gamma, beta, silu, ws);
+  });
+  if (!ok) return CVVAE_EINVAL;
+  int rc = launch_status();
   if (rc) return rc;
   hipLaunchKernelGGL(chan_sums_final_kernel, dim3((C + 31) / 32), dim3(256), 0, stream, (const float*)ws, rows * nsplit, C, sum1,
                      sum2);
@@ -1188,16 +1168,12 @@ int cvvae_pad_fold(int32_t dtype, const void* gp, int32_t B, int32_t T, int32_t 
   const int Tp = T + pad_t_front + pad_t_back, Hp = H + 2 * pad_h, Wp = W + 2 * pad_w;
   long long blocks = ((long long)B * T * H * W * (C / 8) + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-#define CVVAE_FOLD(TY)                                                                                                           \
-  hipLaunchKernelGGL(pad_fold_kernel<TY>, dim3((unsigned)blocks), dim3(256), 0, stream, (const TY*)gp, B, T, H, W, C, Tp, Hp, Wp, \
-                     pad_t_front, pad_h, pad_w, pad_mode_t, pad_mode_hw, (const TY*)add, (TY*)out)
-  switch (dtype) {
-    case CVVAE_BF16: CVVAE_FOLD(__bf16); break;
-    case CVVAE_F16: CVVAE_FOLD(_Float16); break;
-    case CVVAE_F32: CVVAE_FOLD(float); break;
-    default: return CVVAE_EINVAL;
-  }
-#undef CVVAE_FOLD
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using TY = typename decltype(tag)::type;  // (T is the frame count here)
+    hipLaunchKernelGGL(pad_fold_kernel<TY>, dim3((unsigned)blocks), dim3(256), 0, stream, (const TY*)gp, B, T, H, W, C, Tp, Hp, Wp,
+                       pad_t_front, pad_h, pad_w, pad_mode_t, pad_mode_hw, (const TY*)add, (TY*)out);
+  });
+  if (!ok) return CVVAE_EINVAL;
   return (int)hipGetLastError();
 }
 
@@ -1209,16 +1185,12 @@ int cvvae_temporal_attention_bwd(int32_t dtype, const void* q, const void* k, co
   const long long P = (long long)B * S;
   const float scale = 1.0f / sqrtf((float)C);
   const unsigned grid = (unsigned)((P + 3) / 4);
-#define CVVAE_TAB(TY)                                                                                                          \
-  hipLaunchKernelGGL(temporal_attn_bwd_kernel<TY>, dim3(grid), dim3(256), 0, stream, (const TY*)q, (const TY*)k, (const TY*)v, \
-                     (const TY*)go, P, Tn, (long long)S, C, scale, (TY*)gq, (TY*)gk, (TY*)gv)
-  switch (dtype) {
-    case CVVAE_BF16: CVVAE_TAB(__bf16); break;
-    case CVVAE_F16: CVVAE_TAB(_Float16); break;
-    case CVVAE_F32: CVVAE_TAB(float); break;
-    default: return CVVAE_EINVAL;
-  }
-#undef CVVAE_TAB
+  const bool ok = by_dtype(dtype, [&](auto tag) {
+    using TY = typename decltype(tag)::type;
+    hipLaunchKernelGGL(temporal_attn_bwd_kernel<TY>, dim3(grid), dim3(256), 0, stream, (const TY*)q, (const TY*)k, (const TY*)v,
+                       (const TY*)go, P, Tn, (long long)S, C, scale, (TY*)gq, (TY*)gk, (TY*)gv);
+  });
+  if (!ok) return CVVAE_EINVAL;
   return (int)hipGetLastError();
 }
 

@@ -66,6 +66,77 @@ def test_argument_checks_without_gpu():
     assert lib.cvvae_gn_stats(1, None, 1, 1, 128, 128, 32, 1e-6, None, None, None, None, None, None) == -1
 
 
+def _unknown_dtype_calls():
+    """(name, args after the dtype code(s), expected return) of every entry point outside the loss, discriminator and optimiser
+    files that takes a dtype code and decides on it before it touches the HIP runtime.  P stands for a non-NULL HOST pointer; the
+    other arguments are small and valid, so the dtype is the only thing wrong with the call.  cvvae_ncdhw_to_rowpack is not here:
+    it clears its read-ahead tail first, so without a device its return value is the runtime's."""
+    P, EINVAL, EUNSUPPORTED = "P", -1, -2
+    return [
+        ("cvvae_pack_weights", (P, 32, 16, 1, 16, 1, 16, 16, 16, P, None), EINVAL),
+        ("cvvae_pack_weights_fold", (P, 32, 16, 1, 16, 1, 16, 1, 0, 16, 16, P, None), EINVAL),
+        ("cvvae_pack_weights_batched", (P, 1, 512, 32, 16, 1, 16, 1, 16, 16, 16, P, 1 << 20, None), EINVAL),
+        ("cvvae_pack_weights_tfolds", (P, 32, 16, 1, 48, 3, 1, 16, 16, P, None), EINVAL),
+        ("cvvae_pack_weights_upfold", (P, 32, 16, 16, 0, P, None), EINVAL),
+        ("cvvae_pack_weights_upfold_tfolds", (P, 32, 16, 16, P, None), EINVAL),
+        ("cvvae_gn_stats", (P, 1, 64, 32, 32, 4, 1e-6, P, P, P, P, P, None), EINVAL),
+        ("cvvae_gn_silu_apply", (P, 1, 64, 32, 32, P, P, 1, P, None), EINVAL),
+        ("cvvae_gn_bwd_input", (P, P, None, 1, 64, 32, 4, P, P, P, P, 1, P, P, None), EINVAL),
+        ("cvvae_gn_bwd_input_params", (P, P, None, 1, 64, 32, 4, P, P, P, P, 1, P, P, P, P, None), EINVAL),
+        ("cvvae_softmax_bwd_rows", (P, 16, P, 16, 4, 16, 1.0, P, 16, None), EINVAL),
+        ("cvvae_upsample2x_sum", (P, 1, 4, 4, 8, P, None), EINVAL),
+        ("cvvae_layernorm", (P, 4, 32, 1e-6, P, P, P, None), EINVAL),
+        ("cvvae_softmax_rows", (P, 4, 16, 16, P, 16, None), EINVAL),
+        ("cvvae_transpose", (P, 1, 8, 8, 8, 64, P, 8, 64, None), EINVAL),
+        ("cvvae_temporal_attention", (P, P, P, 1, 4, 16, 32, P, None), EINVAL),  # T <= 8: one wave per pixel
+        ("cvvae_temporal_attention", (P, P, P, 1, 9, 16, 32, P, None), EINVAL),  # T > 8: the general kernel
+        ("cvvae_ndhwc_to_rowpack", (P, 1, 3, 2, 4, 4, 8, 0, P, None), EUNSUPPORTED),
+        ("cvvae_ndhwc_to_ncdhw", (P, 1, 3, 2, 4, 4, 8, P, None), EINVAL),
+        ("cvvae_frames_u8_to_ndhwc", (P, 16, 8, P, None), EINVAL),
+        ("cvvae_ncdhw_to_frames_u8", (P, 16, P, None), EINVAL),
+        ("cvvae_conv_out_gather", (P, 1, 2, 4, 4, 3, 28, P, 0, P, None, None), EUNSUPPORTED),
+        ("cvvae_blend", (P, 4, 4, P, 4, 4, 2, 2, 0, None), EINVAL),
+        ("cvvae_channel_sums", (None, P, 32, 1, 64, 32, None, None, None, None, 0, P, None, P, None), EINVAL),
+        ("cvvae_pad_fold", (P, 1, 2, 4, 4, 8, 1, 0, 1, 1, 1, 1, None, P, None), EINVAL),
+        ("cvvae_temporal_attention_bwd", (P, P, P, P, 1, 4, 16, 32, P, P, P, None), EINVAL),
+        ("cvvae_attention_d512", (P, P, P, P, 1, 64, 64, 1.0, None), EUNSUPPORTED),
+        ("cvvae_relu", (P, 64, P, None), EINVAL),
+        ("cvvae_maxpool2x2", (P, 1, 4, 4, 8, P, None), EINVAL),
+        ("cvvae_relu_pool_bwd", (P, P, P, 1, 4, 4, 8, P, None), EINVAL),
+        ("cvvae_lpips_head", (P, P, P, 1, 16, 64, P, P, None), EINVAL),
+        ("cvvae_lpips_head_bwd", (P, P, P, P, 1, 16, 64, P, P, None), EINVAL),
+    ]
+
+
+@pytest.mark.parametrize("bad", [7, -1])
+def test_unknown_dtype_is_refused_before_any_launch(bad):
+    """Pins what each entry point returns for a dtype code that names no element type (recorded from the library as it was before
+    the dispatch was unified: CVVAE_EINVAL in most places, CVVAE_EUNSUPPORTED in a few).  Nothing launches and nothing is
+    dereferenced, so this needs no device."""
+    from cvvae_amd import _lib
+    lib = _lib.load()
+    buf = (ctypes.c_float * 64)()
+    host = ctypes.cast(buf, ctypes.c_void_p)
+
+    def real(args):
+        return [host if a == "P" else a for a in args]
+
+    for name, args, want in _unknown_dtype_calls():
+        assert getattr(lib, name)(bad, *real(args)) == want, name
+    # two codes each: either one unknown is refused, whichever the other is
+    two = [("cvvae_ncdhw_to_ndhwc", ("P", 1, 3, 2, 4, 4, 8, "P", None)),
+           ("cvvae_lpips_scale_in", ("P", 1, 4, 4, "P", "P", 8, "P", None)),
+           ("cvvae_lpips_scale_in_bwd", ("P", 1, 4, 4, 8, "P", "P", None))]
+    for name, args in two:
+        for pair in ((bad, _lib.BF16), (_lib.F32, bad), (bad, bad)):
+            assert getattr(lib, name)(*pair, *real(args)) == -1, (name, pair)
+    # the weight gradient takes its dtype from the descriptor
+    d = _wgrad_desc(_lib, bad, 64, 64, (3, 3, 3), (1, 1, 1), 2, 8, 8)
+    d.in_pix_stride = 64
+    assert lib.cvvae_conv_wgrad(d, host, host, 64, host, host, None) == -1
+    assert lib.cvvae_conv_wgrad_bias(d, host, host, 64, host, host, host, None) == -1
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from cvvae_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
