@@ -19,7 +19,7 @@ nn.GroupNorm(32, c, eps=1e-5) / nn.Linear / nn.LeakyReLU containers), so `state_
                A nin_shortcut whose Cin is no multiple of the 1x1x1 family's 128-channel chunk (main.2: 64) runs as a per-frame (1,3,3)
                conv whose only non-zero tap is the centre (chunk 32): 9x the MFMAs of a 1x1, on a tensor of T/4 x H/4 x W/4 pixels.
 
-Training: ONE autograd node over the input and the parameters (`DiscFn`), a tape and a backward walker in the style of grad3d.py.
+Training: ONE autograd node over the input and the parameters (`DiscFn`), a tape and a backward walker over backward.py's helpers.
 It honours needs_input_grad -- a detached input (the discriminator step) skips the first layer's input gradient, frozen parameters skip
 every weight-gradient / affine-sum launch --, gives `temb_proj.*` None, survives two backward calls (the loss asks
 torch.autograd.grad(g_loss, last_layer, retain_graph=True) before backward()), and returns parameter gradients accumulated in fp32 in
@@ -38,14 +38,16 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib as L
-from . import engine, grad, grad3d, ops
+from . import backward, engine, grad3d, ops
+from .backward import K1, backward_pass, begin_node, block_names, conv_dgrad, conv_param_grads, gn_backward, node_grads, taped, unit_tabs
 from .engine import G32, P1, P2D, ZERO, WeightCache
-from .grad3d import K1, K133, K333
+from .grad3d import K133, K333
 from .loss import weights_init
 
 EPS = 1e-5      # Normalize of models/vae_models.py (the codec's own norms elsewhere in this package use 1e-6)
 SLOPE = 0.2
 S2 = (2, 2, 2)
+GEOM = dict(pad=P1, pad_mode_t=ZERO, pad_mode_hw=ZERO)   # every conv of the network but its first: stride 1, zero padding 1
 
 # the first layer's input gradient: the direct gather kernel (True) or grad3d.dgrad333's zero-stuffed MFMA path (False).  At the
 # training clip [1,3,17,256,256] on an MI355X the gather kernel takes 82 us in bf16 and 147 us in fp32, the zero-stuffed path 384 us
@@ -141,12 +143,6 @@ def disc_forward(wc: WeightCache, x: torch.Tensor, layout: List[Tuple[str, int, 
 # --------------------------------------------------------------------------------------------------------
 # the backward walker
 # --------------------------------------------------------------------------------------------------------
-def _dgrad_p1(wc: WeightCache, g: torch.Tensor, name: str) -> torch.Tensor:
-    """input gradient of a stride-1 3x3x3 conv with zero padding 1: the adjoint of (zero pad, correlate) is the correlation of g
-    with the tap-flipped, transposed weights under the same zero padding -- one launch at the input's own extent"""
-    return ops.conv(g, wc.conv_dgrad(name, K333), pad=P1, pad_mode_t=ZERO, pad_mode_hw=ZERO)
-
-
 def first_layer_dgrad(wc: WeightCache, gv: torch.Tensor, in_shape, cin: int, direct: Optional[bool] = None) -> torch.Tensor:
     """dL/d(input) [B,T,H,W,8] of main.0 (stride 2) given gv = dL/d(its output): the gather kernel, or grad3d.dgrad333's
     zero-stuffed path"""
@@ -157,51 +153,35 @@ def first_layer_dgrad(wc: WeightCache, gv: torch.Tensor, in_shape, cin: int, dir
 
 
 def block_backward(wc: WeightCache, g: torch.Tensor, e: dict, grads: Optional[Dict[str, torch.Tensor]]) -> torch.Tensor:
-    """g = dL/dy of block_forward -> dL/dx; the block's parameter gradients into `grads` (None: frozen)"""
-    pre, x, hq = e["pre"], e["x"], e["hq"]
-    geom = dict(pad=P1, pad_mode_t=ZERO, pad_mode_hw=ZERO)
-    grad3d._conv_param_grads(wc, grads, pre + "conv2", lambda: ops.gn_silu_apply(hq, e["g2"]), g, K333, **geom)
-    g_a2 = _dgrad_p1(wc, g, pre + "conv2")
-    g_hq = grad3d._gn_backward(grads, pre + "norm2", hq, g_a2, grad._unit_tabs(wc, hq, e["hp"], EPS), wc.norm(pre + "norm2"), True)
-    del g_a2
-    g_h = ops.avgpool3d_down_bwd(g_hq, e["h_shape"]) if e["down"] else g_hq
-    grad3d._conv_param_grads(wc, grads, pre + "conv1", lambda: ops.gn_silu_apply(x, e["g1"]), g_h, K333, **geom)
-    g_a1 = _dgrad_p1(wc, g_h, pre + "conv1")
-    del g_h, g_hq
-    skip = g
-    if e["xs"] is not None:
-        sc = pre + "nin_shortcut"
-        if grads is not None:
-            grad._linear_grads(wc, grads, sc, e["xs"], g)
-        skip = grad._dgrad1x1(wc, g, sc)
-    if e["down"]:
-        skip = ops.avgpool3d_down_bwd(skip, tuple(x.shape))
-    return grad3d._gn_backward(grads, pre + "norm1", x, g_a1, grad._unit_tabs(wc, x, e["xp"], EPS), wc.norm(pre + "norm1"), True,
-                               add=skip)
+    """g = dL/dy of block_forward -> dL/dx; the block's parameter gradients into `grads` (None: frozen).  Both convs are 3x3x3 at
+    stride 1 with zero padding 1; a downsampling block goes back through the pool's adjoint on both branches."""
+    pre = e["pre"]
+    return backward.resnet_backward(
+        wc, g, grads, block_names(wc, pre, "nin_shortcut"), e["x"], e["xp"], e["hq"], e["hp"], EPS, gn1=e["g1"], gn2=e["g2"],
+        sc_x=e["xs"], h_shape=e["h_shape"] if e["down"] else None, conv1=(K333, GEOM), conv2=(K333, P1),
+        dgrad1=lambda gh: conv_dgrad(wc, gh, pre + "conv1", K333, P1))
 
 
 def disc_backward(wc: WeightCache, tape: List[dict], gy: torch.Tensor, need_input_grad: bool, need_params: bool):
     """gy = dL/d(logits) NCDHW -> (dL/d(input) NCDHW or None, {parameter name: fp32 gradient})"""
     grads: Optional[Dict[str, torch.Tensor]] = {} if need_params else None
     dtype = wc.p("main.0.weight").dtype
-    gx = None
-    g = None
+    gx = g = None
     for e in reversed(tape):
         if e["op"] == "last":
-            x, name = e["x"], e["name"]
             g = ops.ncdhw_to_ndhwc(gy.contiguous(), ops.kchunk(K333), dtype)          # [B,T',H',W',16], channels 1.. zero
-            grad3d._conv_param_grads(wc, grads, name, x, g, K333, pad=P1, pad_mode_t=ZERO, pad_mode_hw=ZERO)
-            g = _dgrad_p1(wc, g, name)
+            conv_param_grads(wc, grads, e["name"], e["x"], g, K333, **GEOM)
+            g = conv_dgrad(wc, g, e["name"], K333, P1)
         elif e["op"] == "act":
             gv = ops.leaky_bwd(e["y"], g, SLOPE)
-            g = grad3d._gn_backward(grads, e["name"], e["x"], gv, grad._unit_tabs(wc, e["x"], e["xp"], EPS), wc.norm(e["name"]), False)
+            g = gn_backward(grads, e["name"], e["x"], gv, unit_tabs(e["x"], e["xp"], EPS), wc.norm(e["name"]), False)
         elif e["op"] == "block":
             g = block_backward(wc, g, e, grads)
         elif e["op"] == "first":
             if grads is None and not need_input_grad:
                 continue
             gv = ops.leaky_bwd(e["y"], g, SLOPE)
-            grad3d._conv_param_grads(wc, grads, "main.0", e["x"], gv, K333, stride=S2, pad=P1, pad_mode_t=ZERO, pad_mode_hw=ZERO)
+            conv_param_grads(wc, grads, "main.0", e["x"], gv, K333, stride=S2, **GEOM)
             if need_input_grad:
                 gx = ops.ndhwc_to_ncdhw(first_layer_dgrad(wc, gv, e["in_shape"], e["cin"]), e["cin"])
         else:
@@ -215,23 +195,15 @@ class DiscFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x: torch.Tensor, net, names: Tuple[str, ...], *params) -> torch.Tensor:
-        tape: List[dict] = []
-        with torch.cuda.device(x.device):
-            y = disc_forward(net._cache(), x.detach(), net._layout, tape)
-        ctx.net, ctx.tape, ctx.names = net, tape, names
-        ctx.x_dtype = x.dtype
-        ctx.pmeta = [(p.dtype, p.requires_grad, tuple(p.shape)) for p in params]
-        grad3d._remember_versions(ctx, params)
+        y, ctx.tape = taped(x, lambda tape: disc_forward(net._cache(), x.detach(), net._layout, tape))
+        begin_node(ctx, net, x, names, params)
         return y
 
     @staticmethod
     def backward(ctx, gy: torch.Tensor):
-        grad3d._check_unmodified(ctx)
-        need_x = ctx.needs_input_grad[0]
-        need_params = any(req for _, req, _ in ctx.pmeta)
-        with torch.cuda.device(gy.device):
-            gx, grads = disc_backward(ctx.net._cache(), ctx.tape, gy, need_x, need_params)
-        return (gx.to(ctx.x_dtype) if gx is not None else None, None, None, *grad3d._grads_out(ctx.names, ctx.pmeta, grads))
+        with backward_pass(ctx, gy) as grads:
+            gx, grads = disc_backward(ctx.net._cache(), ctx.tape, gy, ctx.need_x, grads is not None)
+        return node_grads(ctx, gx, 2, grads)
 
 
 # --------------------------------------------------------------------------------------------------------

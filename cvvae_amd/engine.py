@@ -4,6 +4,7 @@ This is the host-side mirror of the reference's L1/L2 modules (SURVEY.md 8a rows
 the reference forward it reproduces.  What the reference does as separate ATen ops (F.pad, F.interpolate,
 GroupNorm, SiLU, add, rearrange) is folded into the conv launches -- see include/cvvae.h.
 """
+import contextlib
 import os
 from typing import Dict, Optional, Tuple
 
@@ -17,6 +18,10 @@ P1 = ((1, 1), (1, 1), (1, 1))          # symmetric pad 1 on T,H,W
 PC = ((2, 0), (1, 1), (1, 1))          # causal: T front 2
 P2D = ((0, 0), (1, 1), (1, 1))         # per-frame 3x3
 P0 = ((0, 0), (0, 0), (0, 0))
+
+
+def _wb(pre: str) -> Tuple[str, str]:
+    return pre + ".weight", pre + ".bias"
 
 
 class WeightCache:
@@ -99,20 +104,15 @@ class WeightCache:
                     list(torch._foreach_norm(torch._foreach_add(ps, 0.5), 2, dtype=f64)))
             return torch.stack(sums)
 
+    @contextlib.contextmanager
     def computing_in(self, dtype: Optional[torch.dtype]):
         """context manager: `compute_dtype` = dtype inside, the previous value afterwards (the dtype is per PASS, not per cache: a
         backward under autocast must not leave later export_packed / direct engine calls looking at the 16-bit copies)"""
-        wc = self
-
-        class _Ctx:
-            def __enter__(self_):
-                self_.prev = wc.compute_dtype
-                wc.compute_dtype = dtype
-
-            def __exit__(self_, *exc):
-                wc.compute_dtype = self_.prev
-                return False
-        return _Ctx()
+        prev, self.compute_dtype = self.compute_dtype, dtype
+        try:
+            yield
+        finally:
+            self.compute_dtype = prev
 
     def p(self, name: str) -> torch.nn.Parameter:
         """the module tree's parameter `name`, as nn.Module.get_parameter -- which walks the dotted path on every call (7 us each,
@@ -143,26 +143,47 @@ class WeightCache:
             return c[0]
         return par
 
+    # ---- ONE protocol for every derived form: the entry under its tag is taken when it was made from the parameters the key names, made
+    #      and stored otherwise.  Entries: (key, value), or (key, value, source parameter names) for what export_packed writes.
+    def _key(self, *ps):
+        return tuple((p.data_ptr(), p._version, p.dtype, p.device) for p in ps if p is not None)
+
+    def _src(self, pre: str):
+        """(weight, bias, their key) of the layer `pre`: the source of most forms (the key is _key(weight, bias), spelled out)"""
+        w, b = self.p(pre + ".weight"), self.p(pre + ".bias")
+        return w, b, ((w.data_ptr(), w._version, w.dtype, w.device), (b.data_ptr(), b._version, b.dtype, b.device))
+
+    def _hit(self, tag: str, key):
+        """the value cached under `tag` if its source parameters are still those of `key`, else None"""
+        hit = self._c.get(tag)
+        return hit[1] if hit is not None and hit[0] == key else None
+
+    def _put(self, tag: str, key, value, names: Optional[Tuple[str, ...]] = None):
+        self._c[tag] = (key, value) if names is None else (key, value, names)
+        return value
+
+    def cached(self, tag: str, names: Tuple[str, ...], make):
+        """a derived form of the parameters `names` that is none of the methods below (e.g. another module's repacked table):
+        make(*params) is called when the entry is missing or its source parameters have moved on, exactly as for every packed weight"""
+        ps = [self.p(n) for n in names]
+        key = self._key(*ps)
+        val = self._hit(tag, key)
+        return self._put(tag, key, make(*ps), tuple(names)) if val is None else val
+
     def act_bound(self, norm_pre: str, sigmas: float = 8.0) -> float:
         """upper bound of |SiLU(gamma n + beta)| for a normalised n within `sigmas`: sigmas max|gamma| + max|beta| (one host sync per
         GroupNorm, cached with its parameters).  Elements beyond it lose only their fp6 CORRECTION terms (include/cvvae.h)."""
-        g = self.p(norm_pre + ".weight")
-        b = self.p(norm_pre + ".bias")
-        key = self._key(g, b)
+        g, b, key = self._src(norm_pre)
         tag = norm_pre + "#bound"
-        hit = self._c.get(tag)
-        if hit is None or hit[0] != key:
+        bound = self._hit(tag, key)
+        if bound is None:
             # ONE power of two scales every channel of the operand: channels far below the largest one would land in e3m2's
             # subnormals and lose their corrections, so a norm whose per-channel bounds spread over more than 3 binades (max > 8 x
             # median) returns 0.0 = "no bound": its convs keep the bf8 form, which needs no scale
             bc = (sigmas * g.detach().abs().float() + b.detach().abs().float()).flatten()
             top, mid = float(bc.max()), float(bc.median())
-            hit = (key, max(top, 1e-6) if (top <= 8.0 * max(mid, 1e-30) and top <= self.fp6_bound_cap) else 0.0)
-            self._c[tag] = hit
-        return hit[1]
-
-    def _key(self, *ps):
-        return tuple((p.data_ptr(), p._version, p.dtype, p.device) for p in ps if p is not None)
+            bound = self._put(tag, key, max(top, 1e-6) if (top <= 8.0 * max(mid, 1e-30) and top <= self.fp6_bound_cap) else 0.0)
+        return bound
 
     def conv(self, pre: str, k: Tuple[int, int, int], cin_pad: Optional[int] = None, time_folds: bool = False,
              wscale: Optional[float] = None, act_norm: Optional[str] = None) -> ops.PackedConv:
@@ -170,127 +191,119 @@ class WeightCache:
         wscale (fp32 models): pack with this power-of-two scale (a fused shortcut shares its conv's accumulators);
         act_norm: the GroupNorm whose output (+ SiLU) this stride-1 conv consumes through its prologue -- fast fp32 models then take
         the fp6-correction form with the bound derived from that norm's affine"""
-        w = self.p(pre + ".weight")
-        b = self.p(pre + ".bias")
-        key = self._key(w, b)
+        w, b, key = self._src(pre)
         q6 = (self.fast and self.fast6 and act_norm is not None and w.dtype == torch.float32 and wscale is None
               and tuple(k) in ((3, 3, 3), (1, 3, 3)) and self.act_bound(act_norm) > 0.0)
-        fast = "fp6" if q6 else self.fast
         tag = (pre + "#tf" if time_folds else (pre if wscale is None else f"{pre}#ws{wscale}")) + ("#q6" if q6 else self._q())
-        hit = self._c.get(tag)
-        if hit is not None and hit[0] == key:
-            if q6:
-                hit[1].act_bound = self.act_bound(act_norm)
-            return hit[1]
-        taps = k[0] * k[1] * k[2]
-        co, ci = w.shape[0], w.shape[1]
-        assert w.numel() == co * ci * taps, f"{pre}: weight {tuple(w.shape)} is not a {k} kernel"
-        if time_folds:
-            pw = ops.pack_weight_tfolds(w.detach().reshape(co, ci, *k), b.detach(), cin_pad=cin_pad, fast=fast)
-        else:
-            pw = ops.pack_weight(w.detach().reshape(co, ci, taps), b.detach(), k, cin_pad=cin_pad, wscale=wscale, fast=fast)
-        if q6:
+        pw = self._hit(tag, key)
+        if pw is None:
+            fast = "fp6" if q6 else self.fast
+            taps = k[0] * k[1] * k[2]
+            co, ci = w.shape[0], w.shape[1]
+            assert w.numel() == co * ci * taps, f"{pre}: weight {tuple(w.shape)} is not a {k} kernel"
+            if time_folds:
+                pw = ops.pack_weight_tfolds(w.detach().reshape(co, ci, *k), b.detach(), cin_pad=cin_pad, fast=fast)
+            else:
+                pw = ops.pack_weight(w.detach().reshape(co, ci, taps), b.detach(), k, cin_pad=cin_pad, wscale=wscale, fast=fast)
+            if wscale is not None:  # one scaled form per prefix: older '#ws<scale>' variants (another conv2 scale) are dead weight
+                for t in [t for t in self._c if t.startswith(pre + "#ws") and t != tag]:
+                    del self._c[t]
+            self._put(tag, key, pw, _wb(pre))
+        if q6:  # (on a hit too: the norm's affine may have moved on while the conv's weights stayed)
             pw.act_bound = self.act_bound(act_norm)
-        if wscale is not None:  # one scaled form per prefix: older '#ws<scale>' variants (another conv2 scale) are dead weight
-            for t in [t for t in self._c if t.startswith(pre + "#ws") and t != tag]:
-                del self._c[t]
-        self._c[tag] = (key, pw, (pre + ".weight", pre + ".bias"))
         return pw
 
     def conv_dgrad(self, pre: str, k: Tuple[int, int, int], cin_pad: Optional[int] = None) -> ops.PackedConv:
         """The weights of the INPUT-GRADIENT convolution of a stride-1, zero-padded conv (or linear layer) `pre`: taps flipped,
         Cin and Cout exchanged, no bias -- conv(gy, conv_dgrad(pre)) with the forward's padding is autograd's grad_input
-        (cvvae_amd/grad.py).  k: the forward kernel, (1,1,1) for nn.Linear / 1x1 weights."""
+        (cvvae_amd/backward.py).  k: the forward kernel, (1,1,1) for nn.Linear / 1x1 weights."""
         w = self.p(pre + ".weight")
         key = self._key(w)
         tag = f"{pre}#dgrad"
-        hit = self._c.get(tag)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        taps = k[0] * k[1] * k[2]
-        co, ci = w.shape[0], w.shape[1]
-        assert w.numel() == co * ci * taps, f"{pre}: weight {tuple(w.shape)} is not a {k} kernel"
-        wt = w.detach().reshape(co, ci, taps).flip(2).transpose(0, 1).contiguous()  # [ci, co, taps], taps reversed = flipped in every axis
-        pw = ops.pack_weight(wt, None, k, cin_pad=cin_pad)
-        self._c[tag] = (key, pw, (pre + ".weight",))
+        pw = self._hit(tag, key)
+        if pw is None:
+            taps = k[0] * k[1] * k[2]
+            co, ci = w.shape[0], w.shape[1]
+            assert w.numel() == co * ci * taps, f"{pre}: weight {tuple(w.shape)} is not a {k} kernel"
+            wt = w.detach().reshape(co, ci, taps).flip(2).transpose(0, 1).contiguous()  # [ci, co, taps], taps reversed = flipped in every axis
+            pw = self._put(tag, key, ops.pack_weight(wt, None, k, cin_pad=cin_pad), (pre + ".weight",))
         return pw
 
     def conv_upfold(self, pre: str, tfold: int = 0, time_folds: bool = False, fp6: bool = False) -> ops.PackedConv:
         """Upsample3D conv weights folded into the four 3x2x2 (tfold: 1x2x2) phase kernels (ops.pack_weight_upfold).
         fp6 (fast fp32 models, 3x2x2 phases): the fp6-correction form -- the launch then needs a device-side bound of its operand
         (upsample_conv: the residual stream has no GroupNorm in front)"""
-        w = self.p(pre + ".weight")
-        b = self.p(pre + ".bias")
-        key = self._key(w, b)
+        w, b, key = self._src(pre)
         fp6 = bool(fp6 and self.fast and self.fast6 and w.dtype == torch.float32 and not tfold)
         tag = f"{pre}#upfold{tfold}{'tf' if time_folds else ''}" + ("#q6" if fp6 else self._q())
-        hit = self._c.get(tag)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        pw = ops.pack_weight_upfold(w.detach(), b.detach(), tfold, time_folds=time_folds, fast="fp6" if fp6 else self.fast)
-        self._c[tag] = (key, pw, (pre + ".weight", pre + ".bias"))
+        pw = self._hit(tag, key)
+        if pw is None:
+            pw = self._put(tag, key, ops.pack_weight_upfold(w.detach(), b.detach(), tfold, time_folds=time_folds,
+                                                            fast="fp6" if fp6 else self.fast), _wb(pre))
         return pw
 
     def conv_upfold2d(self, pre: str) -> ops.PackedConv:
         """Upsample2D conv weights [Cout, Cin, 3, 3] as the four folded 1x2x2 phase kernels: the 2-D weight is the centre time tap
         of an otherwise zero 3x3x3 weight (pack_weight_upfold tfold 2 = centre tap only)."""
-        w = self.p(pre + ".weight")
-        b = self.p(pre + ".bias")
-        key = self._key(w, b)
+        w, b, key = self._src(pre)
         tag = f"{pre}#upfold2d" + self._q()
-        hit = self._c.get(tag)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        co, ci, kh, kw = w.shape
-        assert (kh, kw) == (3, 3), f"{pre}: weight {tuple(w.shape)} is not a 3x3 kernel"
-        w3 = torch.zeros((co, ci, 3, 3, 3), dtype=w.dtype, device=w.device)
-        w3[:, :, 1] = w.detach()
-        pw = ops.pack_weight_upfold(w3, b.detach(), 2, fast=self.fast)
-        pw.alg_taps = 9
-        self._c[tag] = (key, pw, (pre + ".weight", pre + ".bias"))
+        pw = self._hit(tag, key)
+        if pw is None:
+            co, ci, kh, kw = w.shape
+            assert (kh, kw) == (3, 3), f"{pre}: weight {tuple(w.shape)} is not a 3x3 kernel"
+            w3 = torch.zeros((co, ci, 3, 3, 3), dtype=w.dtype, device=w.device)
+            w3[:, :, 1] = w.detach()
+            pw = self._put(tag, key, ops.pack_weight_upfold(w3, b.detach(), 2, fast=self.fast), _wb(pre))
+            pw.alg_taps = 9
         return pw
 
     def conv_rowpack(self, pre: str, time_folds: bool = False) -> ops.PackedConv:
         """the networks' first layer ([Cout, 3, 3, 3, 3]) as the (3,3,1) conv over the row-packed input (ops.pack_weight_rowpack)"""
-        w = self.p(pre + ".weight")
-        b = self.p(pre + ".bias")
-        key = self._key(w, b)
+        w, b, key = self._src(pre)
         tag = f"{pre}#rowpack{'tf' if time_folds else ''}"
-        hit = self._c.get(tag)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        pw = ops.pack_weight_rowpack(w.detach(), b.detach(), time_folds=time_folds)
-        self._c[tag] = (key, pw, (pre + ".weight", pre + ".bias"))
+        pw = self._hit(tag, key)
+        if pw is None:
+            pw = self._put(tag, key, ops.pack_weight_rowpack(w.detach(), b.detach(), time_folds=time_folds), _wb(pre))
         return pw
 
     def conv_tapsn(self, pre: str, time_folds: bool = False):
         """the decoders' last layer as the taps-in-N (3,1,1) conv (ops.pack_weight_tapsn) + its fp32 bias"""
-        w = self.p(pre + ".weight")
-        b = self.p(pre + ".bias")
-        key = self._key(w, b)
+        w, b, key = self._src(pre)
         tag = f"{pre}#tapsn{'tf' if time_folds else ''}"
-        hit = self._c.get(tag)
-        if hit is None or hit[0] != key:
-            hit = (key, ops.pack_weight_tapsn(w.detach(), time_folds=time_folds), (pre + ".weight", pre + ".bias"))
-            self._c[tag] = hit
-        bhit = self._c.get(pre + "#f32bias")  # (its own entry: the packed-weight file carries packed weights only)
-        if bhit is None or bhit[0] != key:
-            bhit = (key, b.detach().float().contiguous())
-            self._c[pre + "#f32bias"] = bhit
-        return hit[1], bhit[1]
+        pw = self._hit(tag, key)
+        if pw is None:
+            pw = self._put(tag, key, ops.pack_weight_tapsn(w.detach(), time_folds=time_folds), _wb(pre))
+        bias = self._hit(pre + "#f32bias", key)  # (its own entry, without names: the packed-weight file carries packed weights only)
+        if bias is None:
+            bias = self._put(pre + "#f32bias", key, b.detach().float().contiguous())
+        return pw, bias
 
     def conv_t1(self, pre: str, mode: str, cin_pad: Optional[int] = None) -> ops.PackedConv:
         """3 x kH x kW weights as the single-frame (T = 1) input sees them: time taps summed ('sum') or centre tap ('center')."""
-        w = self.p(pre + ".weight")
-        b = self.p(pre + ".bias")
-        key = self._key(w, b)
+        w, b, key = self._src(pre)
         tag = f"{pre}#t1{mode}" + self._q()
-        hit = self._c.get(tag)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        pw = ops.pack_weight_t1(w.detach(), b.detach(), mode, cin_pad=cin_pad, fast=self.fast)
-        self._c[tag] = (key, pw, (pre + ".weight", pre + ".bias"))
+        pw = self._hit(tag, key)
+        if pw is None:
+            pw = self._put(tag, key, ops.pack_weight_t1(w.detach(), b.detach(), mode, cin_pad=cin_pad, fast=self.fast), _wb(pre))
         return pw
+
+    def bias_sum(self, pre_a: str, pre_b: str) -> torch.Tensor:
+        """fp32 b_a + b_b padded to a multiple of 32: the bias of a conv with a fused 1x1 shortcut"""
+        ba, bb = self.p(pre_a + ".bias"), self.p(pre_b + ".bias")
+        key = self._key(ba, bb)
+        tag = f"{pre_a}+{pre_b}#bias"
+        out = self._hit(tag, key)
+        if out is None:
+            out = self._put(tag, key, torch.zeros(ops.round_up(ba.numel(), 32), dtype=torch.float32, device=ba.device))
+            out[:ba.numel()] = ba.detach().float() + bb.detach().float()
+        return out
+
+    def norm(self, pre: str) -> Tuple[torch.Tensor, torch.Tensor]:
+        g, b, key = self._src(pre)
+        val = self._hit(pre, key)
+        if val is None:
+            val = self._put(pre, key, (g.detach().float().contiguous(), b.detach().float().contiguous()))
+        return val
 
     # ---- persistent packed-weight cache (SURVEY 8f rank 3): the packed forms built so far, keyed by a fingerprint of their source
     #      parameters, so that a later process with the same checkpoint installs them instead of packing again
@@ -345,40 +358,6 @@ class WeightCache:
             # every entry was just checked against the parameters' fingerprints: the first guarded pass may keep them
             self._sum = self._checksum()
         return n
-
-    def bias_sum(self, pre_a: str, pre_b: str) -> torch.Tensor:
-        """fp32 b_a + b_b padded to a multiple of 32: the bias of a conv with a fused 1x1 shortcut"""
-        ba, bb = self.p(pre_a + ".bias"), self.p(pre_b + ".bias")
-        key = self._key(ba, bb)
-        tag = f"{pre_a}+{pre_b}#bias"
-        hit = self._c.get(tag)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        out = torch.zeros(ops.round_up(ba.numel(), 32), dtype=torch.float32, device=ba.device)
-        out[:ba.numel()] = ba.detach().float() + bb.detach().float()
-        self._c[tag] = (key, out)
-        return out
-
-    def cached(self, tag: str, names: Tuple[str, ...], make):
-        """a derived form of the parameters `names` that is none of the above (e.g. another module's repacked table): make(*params)
-        is called when the entry is missing or its source parameters have moved on, exactly as for every packed weight here"""
-        ps = [self.p(n) for n in names]
-        key = self._key(*ps)
-        hit = self._c.get(tag)
-        if hit is None or hit[0] != key:
-            hit = self._c[tag] = (key, make(*ps), tuple(names))
-        return hit[1]
-
-    def norm(self, pre: str) -> Tuple[torch.Tensor, torch.Tensor]:
-        g = self.p(pre + ".weight")
-        b = self.p(pre + ".bias")
-        key = self._key(g, b)
-        hit = self._c.get(pre)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        val = (g.detach().float().contiguous(), b.detach().float().contiguous())
-        self._c[pre] = (key, val)
-        return val
 
     def has(self, name: str) -> bool:
         if name in self._absent:
@@ -446,11 +425,10 @@ def _shortcut_scale_fits(wc: WeightCache, sc_name: str, pw2, dtype) -> bool:
         return True
     w = wc.p(sc_name + ".weight")
     key = wc._key(w)
-    hit = wc._c.get(sc_name + "#absmax")
-    if hit is None or hit[0] != key:
-        hit = (key, float(w.detach().abs().max()))
-        wc._c[sc_name + "#absmax"] = hit
-    return hit[1] * pw2.wscale < 32768.0
+    amax = wc._hit(sc_name + "#absmax", key)
+    if amax is None:
+        amax = wc._put(sc_name + "#absmax", key, float(w.detach().abs().max()))
+    return amax * pw2.wscale < 32768.0
 
 
 def _fused_prologue(x: torch.Tensor, k: Tuple[int, int, int], cout: int) -> bool:

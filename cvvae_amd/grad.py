@@ -7,7 +7,7 @@ backward pass is autograd's input gradient of each of its ops -- no weight gradi
 `engine.constraint_decoder2d`:
 
   conv / linear   grad_input = conv(gy, W with taps flipped and Cin/Cout exchanged), same zero padding  -> the forward MFMA kernel
-                  (WeightCache.conv_dgrad; nn.Conv2d(3x3, padding=1) and nn.Linear of vae_blocks_sd3.py / diffusers Attention)
+                  (backward.conv_dgrad / dgrad1x1; nn.Conv2d(3x3, padding=1) and nn.Linear of vae_blocks_sd3.py / diffusers Attention)
   GroupNorm+SiLU  cvvae_gn_bwd_input (two deterministic passes), the residual skip summed in the same launch
   upsample        Upsample2D = nearest x2 + conv: the conv's input gradient at the upsampled size, then cvvae_upsample2x_sum
   attention       softmax(QK^T/sqrt(C))V per frame: five more products on the 1x1 kernel with per-frame "weights" packed from
@@ -21,52 +21,18 @@ from typing import List, Optional
 import torch
 
 from . import _lib as L
-from . import engine, ops
-from .engine import G32, P2D, ZERO, WeightCache
+from . import backward, engine, ops
+from .backward import K1, backward_pass, begin_node, block_names, conv_dgrad, dgrad1x1, gn_backward, linear_grads, node_grads, taped, unit_tabs
+from .engine import P2D, WeightCache
 
 K2D = (1, 3, 3)
-K1 = (1, 1, 1)
-
-
-def _unit_tabs(wc: WeightCache, x: torch.Tensor, part, eps: float, per_frame: bool = False):
-    """(rstd, -mean*rstd) tables [rows, C] of the GroupNorm over x: the forward's statistics with gamma 1, beta 0"""
-    C = x.shape[-1]
-    one = torch.ones(C, dtype=torch.float32, device=x.device)
-    zero = torch.zeros(C, dtype=torch.float32, device=x.device)
-    if part is not None and not per_frame:
-        return ops.gn_finalize(part, one, zero, eps)
-    return ops.gn_stats(x, one, zero, eps, per_frame=per_frame)
-
-
-def _dgrad3x3(wc: WeightCache, g: torch.Tensor, pre: str, cin_pad=None, **kw) -> torch.Tensor:
-    return ops.conv(g, wc.conv_dgrad(pre, K2D, cin_pad=cin_pad), pad=P2D, pad_mode_hw=ZERO, **kw)
-
-
-def _dgrad1x1(wc: WeightCache, g: torch.Tensor, pre: str, residual=None) -> torch.Tensor:
-    """g [..., Cout] -> g . W  ([..., Cin]) on the flattened pixels of every batch row (+ residual)"""
-    pw = wc.conv_dgrad(pre, K1)
-    y = ops.conv(engine._flat(g), pw, residual=engine._flat(residual) if residual is not None else None)
-    return y.view(*g.shape[:-1], pw.cout)
 
 
 def resnet_backward(wc: WeightCache, g: torch.Tensor, e: dict) -> torch.Tensor:
     """ResnetBlock2D (vae_blocks_sd3.py:368-421): y = conv2(silu(norm2(h))) + shortcut(x), h = conv1(silu(norm1(x))).  g = dL/dy."""
-    pre = e["pre"]
-    x, h = e["x"], e["h"]
-    g_a2 = _dgrad3x3(wc, g, pre + ".conv2")
-    g_h = ops.gn_bwd_input(h, g_a2, _unit_tabs(wc, h, e["hp"], 1e-6), *wc.norm(pre + ".norm2"), silu=True)
-    g_a1 = _dgrad3x3(wc, g_h, pre + ".conv1")
-    skip = _dgrad1x1(wc, g, pre + ".conv_shortcut") if wc.has(pre + ".conv_shortcut.weight") else g
-    return ops.gn_bwd_input(x, g_a1, _unit_tabs(wc, x, e["xp"], 1e-6), *wc.norm(pre + ".norm1"), silu=True, add=skip)
-
-
-def _linear_grads(wc: WeightCache, grads: dict, pre: str, a: torch.Tensor, g: torch.Tensor):
-    """parameter gradients of y = linear(a) (nn.Linear / 1x1 conv `pre`) given g = dL/dy: dW = g^T a on the wgrad kernel, db = sum g"""
-    w = wc.p(pre + ".weight")
-    a5, g5 = a.reshape(a.shape[0], 1, 1, -1, a.shape[-1]), g.reshape(g.shape[0], 1, 1, -1, g.shape[-1])
-    grads[pre + ".weight"] = ops.conv_wgrad(a5.contiguous(), g5.contiguous(), K1, cin=w.shape[1], cout=w.shape[0]).reshape(w.shape)
-    if wc.has(pre + ".bias"):
-        grads[pre + ".bias"] = ops.bias_grad(g5.contiguous(), cout=w.shape[0])
+    pre = e["pre"] + "."
+    return backward.resnet_backward(wc, g, None, block_names(wc, pre, "conv_shortcut"), e["x"], e["xp"], e["h"], e["hp"], 1e-6,
+                                    conv1=(K2D, {}), conv2=(K2D, P2D), dgrad1=lambda gh: conv_dgrad(wc, gh, pre + "conv1", K2D, P2D))
 
 
 def attention_backward(wc: WeightCache, g: torch.Tensor, e: dict, grads: Optional[dict] = None,
@@ -79,7 +45,7 @@ def attention_backward(wc: WeightCache, g: torch.Tensor, e: dict, grads: Optiona
     N, BT = H * W, B * T
     npad = p.shape[-1]
     scale = float(C) ** -0.5
-    g_o = _dgrad1x1(wc, g, proj).view(BT, 1, 1, N, C)                                            # dL/d(PV)
+    g_o = dgrad1x1(wc, g, proj).view(BT, 1, 1, N, C)                                            # dL/d(PV)
     # dL/dP[n,m] = sum_c g_o[n,c] V[m,c]  (fp32), then through the softmax and the score scale
     vw = ops.pack_weight_batched(vv.view(BT, N, C), K1, cin_pad=C, strides=(C, 1, 0), cout=N, cin=C)
     g_p = ops.conv(g_o, vw, out_f32=True, cout_pad=npad)                                          # [BT,1,1,N,npad]
@@ -96,22 +62,19 @@ def attention_backward(wc: WeightCache, g: torch.Tensor, e: dict, grads: Optiona
     qw = ops.pack_weight_batched(ops.transpose(qq.view(BT, N, C)), K1, cin_pad=npad, strides=(N, 1, 0), cout=C, cin=N)
     g_k = ops.conv(gs_t.view(BT, 1, 1, N, npad), qw)
     # back through to_q / to_k / to_v into the normalised input, summed in the launches' residual inputs
-    g_n = _dgrad1x1(wc, g_q, q)
-    g_n = _dgrad1x1(wc, g_k, k, residual=g_n)
-    g_n = _dgrad1x1(wc, g_v, v, residual=g_n)
-    tabs = _unit_tabs(wc, x, None, e["eps"], per_frame=True)
+    g_n = dgrad1x1(wc, g_q, q)
+    g_n = dgrad1x1(wc, g_k, k, residual=g_n)
+    g_n = dgrad1x1(wc, g_v, v, residual=g_n)
+    tabs = unit_tabs(x, None, e["eps"], per_frame=True)
     if grads is not None:
         n = ops.gn_silu_apply(x, e["gn"], silu=False, per_frame=True).view(BT, 1, 1, N, C)   # what to_q / to_k / to_v consumed
-        _linear_grads(wc, grads, proj, e["o"].view(BT, 1, 1, N, C), g.view(BT, 1, 1, N, C))
-        _linear_grads(wc, grads, q, n, g_q)
-        _linear_grads(wc, grads, k, n, g_k)
-        _linear_grads(wc, grads, v, n, g_v)
-        # (add_extra: a block without its own residual -- vae3d's spatial-temporal attention -- passes the gradient of the outer one)
-        gx, grads[norm + ".weight"], grads[norm + ".bias"] = ops.gn_bwd_input_params(
-            x, g_n.view(B, T, H, W, C), tabs, *wc.norm(norm), silu=False, add=g if e["residual"] else add_extra, per_frame=True)
-        return gx
-    return ops.gn_bwd_input(x, g_n.view(B, T, H, W, C), tabs, *wc.norm(norm), silu=False, add=g if e["residual"] else add_extra,
-                            per_frame=True)
+        linear_grads(wc, grads, proj, e["o"].view(BT, 1, 1, N, C), g.view(BT, 1, 1, N, C))
+        linear_grads(wc, grads, q, n, g_q)
+        linear_grads(wc, grads, k, n, g_k)
+        linear_grads(wc, grads, v, n, g_v)
+    # (add_extra: a block without its own residual -- vae3d's spatial-temporal attention -- passes the gradient of the outer one)
+    return gn_backward(grads, norm, x, g_n.view(B, T, H, W, C), tabs, wc.norm(norm), False, add=g if e["residual"] else add_extra,
+                       per_frame=True)
 
 
 def constraint_decoder2d_backward(wc: WeightCache, tape: List[dict], gy: torch.Tensor) -> torch.Tensor:
@@ -122,19 +85,19 @@ def constraint_decoder2d_backward(wc: WeightCache, tape: List[dict], gy: torch.T
     B, T, zin = last["B"], last["T"], last["zin"]
     g = ops.ncdhw_to_ndhwc(gy.contiguous(), 32, dtype)                                           # [b,t,H,W,32], channels 3.. zero
     g = g.view(B * T, 1, g.shape[2], g.shape[3], 32)
-    g = _dgrad3x3(wc, g, "conv_out", cin_pad=32)                                                 # dL/d silu(norm_out(h))
+    g = conv_dgrad(wc, g, "conv_out", K2D, P2D, cin_pad=32)                                      # dL/d silu(norm_out(h))
     x = last["x"]
-    g = ops.gn_bwd_input(x, g, _unit_tabs(wc, x, last["xp"], 1e-6), *wc.norm("conv_norm_out"), silu=True)
+    g = ops.gn_bwd_input(x, g, unit_tabs(x, last["xp"], 1e-6), *wc.norm("conv_norm_out"), silu=True)
     for e in reversed(tape[:-1]):
         if e["op"] == "resnet":
             g = resnet_backward(wc, g, e)
         elif e["op"] == "attn":
             g = attention_backward(wc, g, e)
         elif e["op"] == "up":  # Upsample2D: nearest x2, then conv 3x3
-            g = ops.upsample2x_sum(_dgrad3x3(wc, g, e["pre"]))
+            g = ops.upsample2x_sum(conv_dgrad(wc, g, e["pre"], K2D, P2D))
         else:
             raise AssertionError(e["op"])
-    gz = ops.conv(g, wc.conv_dgrad("conv_in", K2D), pad=P2D, pad_mode_hw=ZERO, out_mode=L.OUT_NCDHW)   # [b*t, zin, 1, h, w]
+    gz = conv_dgrad(wc, g, "conv_in", K2D, P2D, out_mode=L.OUT_NCDHW)   # [b*t, zin, 1, h, w]
     return gz.view(B, T, zin, gz.shape[3], gz.shape[4]).transpose(1, 2).contiguous()
 
 
@@ -143,18 +106,14 @@ class ConstraintDecoderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z: torch.Tensor, net) -> torch.Tensor:
-        tape: List[dict] = []
-        with torch.cuda.device(z.device):
-            y = engine.constraint_decoder2d(net._cache(), z.detach(), net._cfg, tape)
-        ctx.net, ctx.tape, ctx.zdtype = net, tape, z.dtype
-        ctx.cd = net._cache().compute_dtype  # (torch.autocast: the backward thread runs outside the context -- same weights, same dtype)
+        y, ctx.tape = taped(z, lambda tape: engine.constraint_decoder2d(net._cache(), z.detach(), net._cfg, tape))
+        begin_node(ctx, net, z, cd=net._cache().compute_dtype)
         return y
 
     @staticmethod
     def backward(ctx, gy: torch.Tensor):
-        net, tape = ctx.net, ctx.tape
         # the tape (block inputs, statistics records, attention operands) is kept until autograd frees the node, so a second
         # backward through it (retain_graph=True, two losses) walks the same tape and gives the same bits
-        with torch.cuda.device(gy.device), net._cache().computing_in(ctx.cd):
-            gz = constraint_decoder2d_backward(net._cache(), tape, gy)
-        return gz.to(ctx.zdtype), None
+        with backward_pass(ctx, gy):
+            gz = constraint_decoder2d_backward(ctx.net._cache(), ctx.tape, gy)
+        return node_grads(ctx, gz, 1, None)

@@ -14,7 +14,7 @@ vae3d_sd3 family:
                        three small layers; a first version)
       weight gradient  `cvvae_conv_wgrad` over the operand the forward multiplied (GroupNorm + SiLU re-applied by
                        `cvvae_gn_silu_apply`; padding by the kernel's own coordinate map), bias gradient `cvvae_channel_sums`
-  conv 1x3x3 zero padding, 1x1 shortcut, nn.Linear   as in grad.py + the same wgrad / bias kernels
+  conv 1x3x3 zero padding, 1x1 shortcut, nn.Linear   backward.conv_dgrad / dgrad1x1 + the same wgrad / bias kernels (backward.py)
   GroupNorm (+ SiLU)  input gradient `cvvae_gn_bwd_input`, affine gradients `cvvae_channel_sums` (both from the forward's statistics)
   attention           grad.attention_backward with its parameter gradients switched on
 
@@ -37,37 +37,14 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import _lib as L
-from . import engine, grad, ops
+from . import backward, grad, ops
+from .backward import (K1, backward_pass, begin_node, block_names, conv_param_grads, dgrad1x1, gn_backward, linear_grads, node_grads,
+                       taped, unit_tabs)
 from .engine import P2D, REP, ZERO, WeightCache
 
 K333 = (3, 3, 3)
 K133 = (1, 3, 3)
-K1 = (1, 1, 1)
 FULL = ((2, 2), (2, 2), (2, 2))  # zero padding of the full correlation of a 3x3x3 kernel
-
-
-def _conv_param_grads(wc: WeightCache, grads: Optional[Dict[str, torch.Tensor]], pre: str, a, g: torch.Tensor, k, **geom):
-    """dW, db of `pre` (a conv over operand a with output gradient g); grads None = a frozen network: nothing to do.
-    a: the operand, or a callable that produces it (so that a frozen pass does not re-create operands it never reads)"""
-    if grads is None:
-        return
-    if callable(a):
-        a = a()
-    w = wc.p(pre + ".weight")
-    if wc.has(pre + ".bias"):   # (the bias gradient comes out of the weight-gradient launch where the kernel fuses it)
-        dw, grads[pre + ".bias"] = ops.conv_wgrad(a, g, k, cin=w.shape[1], cout=w.shape[0], bias=True, **geom)
-    else:
-        dw = ops.conv_wgrad(a, g, k, cin=w.shape[1], cout=w.shape[0], **geom)
-    grads[pre + ".weight"] = dw.reshape(w.shape)
-
-
-def _gn_backward(grads, name: str, x, g, tabs, affine, silu: bool, add=None):
-    """input gradient of act(GroupNorm(x)) (+ add), and -- trainable network -- the norm's affine gradients into `grads`"""
-    if grads is None:
-        return ops.gn_bwd_input(x, g, tabs, *affine, silu=silu, add=add)
-    gx, grads[name + ".weight"], grads[name + ".bias"] = ops.gn_bwd_input_params(x, g, tabs, *affine, silu=silu, add=add)
-    return gx
 
 
 def dgrad333(wc: WeightCache, g: torch.Tensor, pre: str, pad, mode_t: int, mode_hw: int, in_shape, stride=(1, 1, 1),
@@ -103,32 +80,14 @@ def dgrad333_replicate(wc, g, pre, pad_t, in_shape, stride=(1, 1, 1), add=None):
 
 def sd3_resnet_backward(wc: WeightCache, g: torch.Tensor, e: dict, grads: Dict[str, torch.Tensor]) -> torch.Tensor:
     """ResnetBlock3D of either family (vae_blocks3d_sd3.py:517-569, vae_models.py:390-410): y = conv2(silu(norm2(h))) + shortcut(x),
-    h = conv1(silu(norm1(x))); g = dL/dy.  Padding, GroupNorm eps and the shortcut's name come with the tape entry."""
-    pre, x, h = e["pre"], e["x"], e["h"]
-    pad, mt, mhw, eps = e["pad"], e["mode_t"], e["mode_hw"], e["eps"]
-    B, T, H, W, _ = x.shape
-    # conv2: per-frame 3x3, zero padding, over a2 = silu(norm2(h))
-    _conv_param_grads(wc, grads, pre + ".conv2", lambda: ops.gn_silu_apply(h, e["g2"]), g, K133, pad=P2D)
-    g_a2 = ops.conv(g, wc.conv_dgrad(pre + ".conv2", K133), pad=P2D, pad_mode_hw=ZERO)
-    tabs2 = grad._unit_tabs(wc, h, e["hp"], eps)
-    n2 = wc.norm(pre + ".norm2")
-    g_h = _gn_backward(grads, pre + ".norm2", h, g_a2, tabs2, n2, True)
-    del g_a2
-    # conv1: 3x3x3 over a1 = silu(norm1(x))
-    _conv_param_grads(wc, grads, pre + ".conv1", lambda: ops.gn_silu_apply(x, e["g1"]), g_h, K333, pad=pad, pad_mode_t=mt,
-                      pad_mode_hw=mhw)
-    g_a1 = dgrad333(wc, g_h, pre + ".conv1", pad, mt, mhw, (B, T, H, W))
-    # skip branch
-    sc = pre + e["sc"]
-    if wc.has(sc + ".weight"):
-        if grads is not None:
-            grad._linear_grads(wc, grads, sc, x.view(B, 1, 1, -1, x.shape[-1]), g.view(B, 1, 1, -1, g.shape[-1]))
-        skip = grad._dgrad1x1(wc, g, sc)
-    else:
-        skip = g
-    tabs1 = grad._unit_tabs(wc, x, e["xp"], eps)
-    n1 = wc.norm(pre + ".norm1")
-    return _gn_backward(grads, pre + ".norm1", x, g_a1, tabs1, n1, True, add=skip)
+    h = conv1(silu(norm1(x))); g = dL/dy.  Padding, GroupNorm eps and the shortcut's name come with the tape entry: conv2 is the
+    per-frame 3x3 with zero padding, conv1 the 3x3x3 whose input gradient is dgrad333."""
+    pre, x = e["pre"] + ".", e["x"]
+    pad, mt, mhw = e["pad"], e["mode_t"], e["mode_hw"]
+    return backward.resnet_backward(
+        wc, g, grads, block_names(wc, pre, e["sc"][1:]), x, e["xp"], e["h"], e["hp"], e["eps"], gn1=e["g1"], gn2=e["g2"], sc_x=x,
+        conv1=(K333, dict(pad=pad, pad_mode_t=mt, pad_mode_hw=mhw)), conv2=(K133, P2D),
+        dgrad1=lambda gh: dgrad333(wc, gh, pre + "conv1", pad, mt, mhw, tuple(x.shape[:4])))
 
 
 def _unshuffle_time(g: torch.Tensor) -> torch.Tensor:
@@ -147,8 +106,8 @@ def sd3_upsample_backward(wc: WeightCache, g: torch.Tensor, e: dict, grads: Dict
     B, T, H, W, C = x.shape
     gc = _unshuffle_time(g) if e["up_time"] else g
     # (the operand: F.interpolate(scale=(1,2,2), mode="nearest") of x, materialised for the weight gradient only)
-    _conv_param_grads(wc, grads, pre, lambda: x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3), gc, K333, pad=pad,
-                      pad_mode_t=e["mode_t"], pad_mode_hw=e["mode_hw"])
+    conv_param_grads(wc, grads, pre, lambda: x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3), gc, K333, pad=pad,
+                     pad_mode_t=e["mode_t"], pad_mode_hw=e["mode_hw"])
     gup = dgrad333(wc, gc, pre, pad, e["mode_t"], e["mode_hw"], (B, T, 2 * H, 2 * W))
     return ops.upsample2x_sum(gup.view(B * T, 1, 2 * H, 2 * W, C)).view(B, T, H, W, C)
 
@@ -161,14 +120,14 @@ def temporal_attention_backward(wc: WeightCache, g: torch.Tensor, e: dict, grads
     B, T, H, W, C = h.shape
     flat = lambda t: t.view(B, 1, 1, -1, t.shape[-1])  # noqa: E731
     if grads is not None:
-        grad._linear_grads(wc, grads, a + ".proj_out_t", flat(e["o"]), flat(g))
-    g_o = grad._dgrad1x1(wc, g, a + ".proj_out_t")
+        linear_grads(wc, grads, a + ".proj_out_t", flat(e["o"]), flat(g))
+    g_o = dgrad1x1(wc, g, a + ".proj_out_t")
     g_q, g_k, g_v = ops.temporal_attention_bwd(e["q"], e["k"], e["v"], g_o)
     g_n = None
     for name, gg in ((".q_t", g_q), (".k_t", g_k), (".v_t", g_v)):
         if grads is not None:
-            grad._linear_grads(wc, grads, a + name, flat(n), flat(gg))
-        g_n = grad._dgrad1x1(wc, gg, a + name, residual=g_n)
+            linear_grads(wc, grads, a + name, flat(n), flat(gg))
+        g_n = dgrad1x1(wc, gg, a + name, residual=g_n)
     g_h, dg, db = ops.layernorm_bwd(h, g_n, *wc.norm(a + ".norm_t"), 1e-5)
     if grads is not None:
         grads[a + ".norm_t.weight"], grads[a + ".norm_t.bias"] = dg, db
@@ -184,13 +143,11 @@ def tail_backward(wc: WeightCache, last: dict, gy: torch.Tensor, grads: Optional
     cout = wc.p("conv_out.weight").shape[0]
     g = ops.ncdhw_to_ndhwc(gy.contiguous(), ops.round_up(cout, 16), dtype)                      # [B,T',h,w,Cpad], pad channels zero
     x = last["x"]
-    _conv_param_grads(wc, grads, "conv_out", lambda: ops.gn_silu_apply(x, last["g"]), g, K333, pad=pad, pad_mode_t=mt, pad_mode_hw=mhw)
+    conv_param_grads(wc, grads, "conv_out", lambda: ops.gn_silu_apply(x, last["g"]), g, K333, pad=pad, pad_mode_t=mt, pad_mode_hw=mhw)
     if not need_input_grad and grads is None:
         return None
     g = dgrad333(wc, g, "conv_out", pad, mt, mhw, tuple(x.shape[:4]))
-    tabs = grad._unit_tabs(wc, x, last["xp"], last["eps"])
-    no = wc.norm(last["norm"])
-    return _gn_backward(grads, last["norm"], x, g, tabs, no, True)
+    return gn_backward(grads, last["norm"], x, g, unit_tabs(x, last["xp"], last["eps"]), wc.norm(last["norm"]), True)
 
 
 def body_backward(wc: WeightCache, tape: List[dict], g: torch.Tensor, grads: Optional[Dict[str, torch.Tensor]], need_input_grad: bool):
@@ -208,26 +165,21 @@ def body_backward(wc: WeightCache, tape: List[dict], g: torch.Tensor, grads: Opt
             outer = None
         elif e["op"] == "down3d":
             xin = e["x"]
-            _conv_param_grads(wc, grads, e["pre"], xin, g, K333, stride=e["stride"], pad=e["pad"], pad_mode_t=e["mode_t"],
-                              pad_mode_hw=e["mode_hw"])
+            conv_param_grads(wc, grads, e["pre"], xin, g, K333, stride=e["stride"], pad=e["pad"], pad_mode_t=e["mode_t"],
+                             pad_mode_hw=e["mode_hw"])
             g = dgrad333(wc, g, e["pre"], e["pad"], e["mode_t"], e["mode_hw"], tuple(xin.shape[:4]), stride=e["stride"])
         elif e["op"] == "up3d":
             g = sd3_upsample_backward(wc, g, e, grads)
-        elif e["op"] == "conv_in":   # the encoder's first layer over the clip
+        elif e["op"] in ("conv_in", "dec_in"):   # the first layer: over the clip (encoder) / the channel-padded NDHWC latent (decoder)
             if grads is None and not need_input_grad:
                 continue
-            xin = e["x"] if e["ndhwc_in"] else ops.ncdhw_to_ndhwc(e["x"], 16, dtype)           # [B,T,H,W,16], channels 3.. zero
-            _conv_param_grads(wc, grads, "conv_in", xin, g, K333, pad=e["pad"], pad_mode_t=e["mode_t"], pad_mode_hw=e["mode_hw"])
+            dec = e["op"] == "dec_in"
+            xin = e["x"] if dec or e["ndhwc_in"] else ops.ncdhw_to_ndhwc(e["x"], 16, dtype)      # [B,T,H,W,16], channels 3.. zero
+            conv_param_grads(wc, grads, "conv_in", xin, g, K333, pad=e["pad"], pad_mode_t=e["mode_t"], pad_mode_hw=e["mode_hw"])
             if need_input_grad:
-                # (conv_in's weights as a 128 -> 3-channel transposed kernel; the gradient tensor is channel-padded to 8)
+                # (the encoder's conv_in as a 128 -> 3-channel transposed kernel; the gradient tensor is channel-padded to 8)
                 gi = dgrad333(wc, g, "conv_in", e["pad"], e["mode_t"], e["mode_hw"], tuple(xin.shape[:4]))
-                gx = ops.ndhwc_to_ncdhw(gi, wc.p("conv_in.weight").shape[1])
-        elif e["op"] == "dec_in":    # the decoder's first layer over the (channel-padded NDHWC) latent
-            xin = e["x"]
-            _conv_param_grads(wc, grads, "conv_in", xin, g, K333, pad=e["pad"], pad_mode_t=e["mode_t"], pad_mode_hw=e["mode_hw"])
-            if need_input_grad:
-                gi = dgrad333(wc, g, "conv_in", e["pad"], e["mode_t"], e["mode_hw"], tuple(xin.shape[:4]))
-                gx = ops.ndhwc_to_ncdhw(gi, e["zin"])
+                gx = ops.ndhwc_to_ncdhw(gi, e["zin"] if dec else wc.p("conv_in.weight").shape[1])
         else:
             raise AssertionError(e["op"])
     return gx
@@ -247,26 +199,6 @@ sd3_encoder_backward = sd3_net_backward  # (the encoder's tape through the commo
 sd3_decoder_backward = sd3_net_backward
 
 
-def _grads_out(names, pmeta, grads):
-    """the fp32 gradients in the parameters' order, shapes and dtypes.  The conversions of a 16-bit model are ONE multi-tensor copy
-    (a `.to(dt)` per parameter was 244 five-microsecond launches per training step of the sd3 pair)."""
-    out, src, dst = [], [], []
-    for name, (dt, req, shape) in zip(names, pmeta):
-        gq = grads.get(name)
-        if not (req and gq is not None):
-            out.append(None)
-            continue
-        gq = gq.reshape(shape)
-        if gq.dtype != dt:
-            src.append(gq)
-            gq = torch.empty(shape, dtype=dt, device=gq.device)
-            dst.append(gq)
-        out.append(gq)
-    if dst:
-        torch._foreach_copy_(dst, src)
-    return out
-
-
 # A network is TWO autograd nodes: the body (everything up to the input h of the last GroupNorm) and the tail (GroupNorm + SiLU +
 # conv_out).  The reference's adversarial loss asks for  torch.autograd.grad(loss, decoder.get_last_layer(), retain_graph=True)  twice
 # per step (`calculate_adaptive_weight`, lvdm/modules/autoencoding/losses/discriminator_loss.py:211-220; get_last_layer =
@@ -280,50 +212,25 @@ def _is_tail(name: str) -> bool:
     return name.rsplit(".", 1)[0] in TAIL_PREFIXES
 
 
-# The backward reads the weights LIVE (packed input-gradient forms, norm affines) instead of saving them on the tape.  PyTorch's own
-# conv backward would raise "one of the variables needed for gradient computation has been modified by an inplace operation" when
-# a parameter changes between forward and backward (an optimizer.step() under retain_graph, a GAN's generator / discriminator
-# alternation on one graph); so does this one: the parameters' (storage, version) are remembered by the forward and checked.
-def _remember_versions(ctx, params):
-    ctx.pobj = params
-    ctx.pver = [(p.data_ptr(), p._version) for p in params]
-
-
-def _check_unmodified(ctx):
-    for name, p, was in zip(ctx.names, ctx.pobj, ctx.pver):
-        if (p.data_ptr(), p._version) != was:
-            raise RuntimeError(f"parameter {name} of {type(ctx.net).__name__} was modified (in place, or replaced) between the forward "
-                               f"and this backward pass: the taped activations belong to the old weights (version {was[1]} -> "
-                               f"{p._version}).  Run the backward before optimizer.step(), or re-run the forward.")
-
-
 class Net3DBodyFn(torch.autograd.Function):
     """(x, *body parameters) -> h, the NDHWC input of the network's last GroupNorm (the whole inference program runs here, with a
     tape; its output y waits in `box` for Net3DTailFn); backward = body_backward"""
 
     @staticmethod
     def forward(ctx, x: torch.Tensor, net, names: Tuple[str, ...], box: dict, *params) -> torch.Tensor:
-        tape: List[dict] = []
-        with torch.cuda.device(x.device):
-            y = type(net)._program(net._cache(), x.detach(), dict(net._cfg), tape)
+        y, tape = taped(x, lambda tape: type(net)._program(net._cache(), x.detach(), dict(net._cfg), tape))
         assert tape[-1]["op"] == "out3d" and tape[-1]["norm"] in TAIL_PREFIXES, tape[-1]["op"]
-        box["y"], box["last"] = y, tape[-1]
-        ctx.net, ctx.tape, ctx.names = net, tape[:-1], names
-        ctx.cd = box["cd"] = net._cache().compute_dtype  # (autocast: the backward runs outside the context -- same 16-bit weight copies)
-        ctx.x_dtype, ctx.need_x = x.dtype, x.requires_grad
-        ctx.pmeta = [(p.dtype, p.requires_grad, tuple(p.shape)) for p in params]
-        _remember_versions(ctx, params)
+        box["y"], box["last"], box["cd"] = y, tape[-1], net._cache().compute_dtype
+        ctx.tape = tape[:-1]
+        begin_node(ctx, net, x, names, params, box["cd"])
         # (a view: autograd owns the returned tensor object, the tape keeps reading the same storage)
         return tape[-1]["x"].view_as(tape[-1]["x"])
 
     @staticmethod
     def backward(ctx, gh: torch.Tensor):
-        need_params = any(req for _, req, _ in ctx.pmeta)
-        grads: Optional[Dict[str, torch.Tensor]] = {} if need_params else None
-        _check_unmodified(ctx)
-        with torch.cuda.device(gh.device), ctx.net._cache().computing_in(ctx.cd):
+        with backward_pass(ctx, gh) as grads:
             gx = body_backward(ctx.net._cache(), ctx.tape, gh.contiguous(), grads, ctx.need_x)
-        return (gx.to(ctx.x_dtype) if gx is not None else None, None, None, None, *_grads_out(ctx.names, ctx.pmeta, grads or {}))
+        return node_grads(ctx, gx, 3, grads)
 
 
 class Net3DTailFn(torch.autograd.Function):
@@ -331,20 +238,15 @@ class Net3DTailFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h: torch.Tensor, net, names: Tuple[str, ...], box: dict, *params) -> torch.Tensor:
-        ctx.net, ctx.last, ctx.names, ctx.cd = net, box.pop("last"), names, box.pop("cd")
-        ctx.need_h = h.requires_grad
-        ctx.pmeta = [(p.dtype, p.requires_grad, tuple(p.shape)) for p in params]
-        _remember_versions(ctx, params)
+        ctx.last = box.pop("last")
+        begin_node(ctx, net, h, names, params, box.pop("cd"))
         return box.pop("y")
 
     @staticmethod
     def backward(ctx, gy: torch.Tensor):
-        need_params = any(req for _, req, _ in ctx.pmeta)
-        grads: Optional[Dict[str, torch.Tensor]] = {} if need_params else None
-        _check_unmodified(ctx)
-        with torch.cuda.device(gy.device), ctx.net._cache().computing_in(ctx.cd):
-            gh = tail_backward(ctx.net._cache(), ctx.last, gy, grads, need_input_grad=ctx.need_h)
-        return (gh if ctx.need_h else None, None, None, None, *_grads_out(ctx.names, ctx.pmeta, grads or {}))
+        with backward_pass(ctx, gy) as grads:
+            gh = tail_backward(ctx.net._cache(), ctx.last, gy, grads, need_input_grad=ctx.need_x)
+        return node_grads(ctx, gh if ctx.need_x else None, 3, grads)
 
 
 class Net3DRecomputeFn(torch.autograd.Function):
@@ -359,24 +261,19 @@ class Net3DRecomputeFn(torch.autograd.Function):
     def forward(ctx, x: torch.Tensor, net, names: Tuple[str, ...], *params) -> torch.Tensor:
         with torch.cuda.device(x.device):
             y = type(net)._program(net._cache(), x.detach(), dict(net._cfg))
-        ctx.net, ctx.names, ctx.x = net, names, x.detach()
-        ctx.cd = net._cache().compute_dtype
-        ctx.x_dtype, ctx.need_x = x.dtype, x.requires_grad
-        ctx.pmeta = [(p.dtype, p.requires_grad, tuple(p.shape)) for p in params]
-        _remember_versions(ctx, params)
+        ctx.x = x.detach()
+        begin_node(ctx, net, x, names, params, net._cache().compute_dtype)
         return y
 
     @staticmethod
     def backward(ctx, gy: torch.Tensor):
-        _check_unmodified(ctx)
-        need_params = any(req for _, req, _ in ctx.pmeta)
         net = ctx.net
-        with torch.cuda.device(gy.device), net._cache().computing_in(ctx.cd):
+        with backward_pass(ctx, gy) as grads:
             tape: List[dict] = []
             type(net)._program(net._cache(), ctx.x, dict(net._cfg), tape)  # same launches, same bits as the forward's pass
-            gx, grads = sd3_net_backward(net._cache(), tape, gy.contiguous(), need_input_grad=ctx.need_x, need_params=need_params)
+            gx, grads = sd3_net_backward(net._cache(), tape, gy.contiguous(), need_input_grad=ctx.need_x, need_params=grads is not None)
             del tape
-        return (gx.to(ctx.x_dtype) if gx is not None else None, None, None, *_grads_out(ctx.names, ctx.pmeta, grads))
+        return node_grads(ctx, gx, 2, grads)
 
 
 class BlendFn(torch.autograd.Function):

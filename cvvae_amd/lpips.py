@@ -14,7 +14,7 @@ channel-normalised, their squared difference weighted by a 1x1 "lin" layer and a
 
 and, as ONE autograd node, the input gradient of all of it: cvvae_lpips_head_bwd per level, cvvae_relu_pool_bwd (ReLU backward,
 pooling backward and the sum of the two branches in one pass), the convolutions' input gradients on the same conv kernel with
-transposed, tap-flipped weights (WeightCache.conv_dgrad), cvvae_lpips_scale_in_bwd.  The trunk is frozen: no weight gradients.
+transposed, tap-flipped weights (backward.conv_dgrad), cvvae_lpips_scale_in_bwd.  The trunk is frozen: no weight gradients.
 Only the half of the batch whose argument requires a gradient is back-propagated (in the training step: `reconstructions`).
 
 The compute dtype is the parameters' dtype: fp32 modules run as exact split-precision CVVAE_F32, `.half()` / `.bfloat16()` modules on
@@ -33,6 +33,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .backward import conv_dgrad
 from .engine import P2D, ZERO, WeightCache
 
 K2D = (1, 3, 3)
@@ -126,7 +127,7 @@ def _backward(m: "LPIPS", tape: List[list], gout: torch.Tensor, need0: bool, nee
             yj = ys[j][:, lo:lo + F]
             g = ops.relu_pool_bwd(yj, gt, g) if j == len(convs) - 1 else ops.relu_pool_bwd(yj, g, None)
             first = convs[j] == 0  # 64 -> 3 channels: stored with 8 (16-byte pixels), channels 3.. zero
-            g = ops.conv(g, wc.conv_dgrad(f"net.{name}.{convs[j]}", K2D), pad=P2D, pad_mode_hw=ZERO, cout_pad=8 if first else None)
+            g = conv_dgrad(wc, g, f"net.{name}.{convs[j]}", K2D, P2D, cout_pad=8 if first else None)
     return g
 
 

@@ -148,6 +148,68 @@ def test_packed_weight_cache_skips_stale_entries(tmp_path):
         assert torch.equal(m2.encode(x).latent_dist.mode(), z_new)
 
 
+# every packed form's tag as the cache has always spelled it (an export_packed file written before WeightCache's methods shared one
+# lookup must still install, and each method must then HIT its entry): tag -> (source parameters, the lookup that must hit)
+PACKED_TAGS = {
+    "a": (("a.weight", "a.bias"), lambda wc: wc.conv("a", (3, 3, 3))),
+    "a#tf": (("a.weight", "a.bias"), lambda wc: wc.conv("a", (3, 3, 3), time_folds=True)),
+    "a#ws0.5": (("a.weight", "a.bias"), lambda wc: wc.conv("a", (3, 3, 3), wscale=0.5)),
+    "a#dgrad": (("a.weight",), lambda wc: wc.conv_dgrad("a", (3, 3, 3))),
+    "a#upfold0": (("a.weight", "a.bias"), lambda wc: wc.conv_upfold("a")),
+    "a#upfold1tf": (("a.weight", "a.bias"), lambda wc: wc.conv_upfold("a", tfold=1, time_folds=True)),
+    "b#upfold2d": (("b.weight", "b.bias"), lambda wc: wc.conv_upfold2d("b")),
+    "a#rowpack": (("a.weight", "a.bias"), lambda wc: wc.conv_rowpack("a")),
+    "a#rowpacktf": (("a.weight", "a.bias"), lambda wc: wc.conv_rowpack("a", time_folds=True)),
+    "a#tapsn": (("a.weight", "a.bias"), lambda wc: wc.conv_tapsn("a")[0]),
+    "a#tapsntf": (("a.weight", "a.bias"), lambda wc: wc.conv_tapsn("a", time_folds=True)[0]),
+    "a#t1sum": (("a.weight", "a.bias"), lambda wc: wc.conv_t1("a", "sum")),
+    "a#t1center": (("a.weight", "a.bias"), lambda wc: wc.conv_t1("a", "center")),
+}
+
+
+def test_an_exported_blob_in_the_old_tag_format_is_installed_and_hit_by_every_packed_form(monkeypatch):
+    """import_packed of a blob with literal tags covering the seven packed forms (conv, conv_dgrad, conv_upfold, conv_upfold2d,
+    conv_rowpack, conv_tapsn, conv_t1): every tag is accepted, and the corresponding method returns the installed object without
+    calling a packer; entries without names (norm tables, the taps-in-N layer's fp32 bias) stay out of export_packed"""
+    from cvvae_amd import engine, ops
+
+    class Two(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.a = torch.nn.Conv3d(8, 8, 3)
+            self.b = torch.nn.Conv2d(8, 8, 3)
+            self.n = torch.nn.GroupNorm(4, 8)
+    m = Two()
+    wc = engine.WeightCache(m)
+    blob = {}
+    for i, (tag, (names, _)) in enumerate(PACKED_TAGS.items()):
+        pw = dict(w=torch.full((4,), float(i)), bias=torch.zeros(32), cout=8, cin=32, k=[3, 3, 3], cin_real=8, folded=False,
+                  batch_stride=0, alg_taps=0, time_folds=False, wscale=1.0, dt=-1, act_bound=0.0)
+        blob[tag] = {"names": list(names), "fp": [engine.WeightCache._fingerprint(m.get_parameter(n)) for n in names], "pw": pw}
+    assert wc.import_packed(blob) == len(PACKED_TAGS)
+    packed = []
+    with emu_ops.patched():
+        for name in ("pack_weight", "pack_weight_tfolds", "pack_weight_t1", "pack_weight_upfold", "pack_weight_rowpack", "pack_weight_tapsn"):
+            monkeypatch.setattr(ops, name, lambda *a, _n=name, **k: packed.append(_n))
+        for i, (tag, (_, lookup)) in enumerate(PACKED_TAGS.items()):
+            got = lookup(wc)
+            assert isinstance(got, ops.PackedConv) and float(got.w[0]) == float(i) and got.k == (3, 3, 3), tag
+        assert packed == []
+        wc.norm("n")
+        assert sorted(wc.export_packed()) == sorted(PACKED_TAGS)          # (a#f32bias and the norm table carry no names)
+        assert {"n", "a#f32bias"} <= set(wc._c) and all(len(wc._c[t]) == 2 for t in ("n", "a#f32bias"))
+        # a new scale drops its stale '#ws<scale>' sibling; the parameters moving on re-packs
+        monkeypatch.setattr(ops, "pack_weight", lambda *a, **k: packed.append("pack_weight") or ops.PackedConv(
+            torch.zeros(1), torch.zeros(32), 8, 32, (3, 3, 3)))
+        wc.conv("a", (3, 3, 3), wscale=0.25)
+        assert "a#ws0.25" in wc._c and "a#ws0.5" not in wc._c and packed == ["pack_weight"]
+        with torch.no_grad():
+            m.a.weight.mul_(2.0)
+        wc.conv_dgrad("a", (3, 3, 3))
+        assert packed == ["pack_weight"] * 2
+        monkeypatch.undo()
+
+
 def test_encode_latents_flatten_frames_matches_reference_layout():
     """DiffusionEngineFor3DVAE.encode_first_stage returns '(b t) c h w' for clips as well (diffusion.py:380-385)"""
     m = build("sd3", {}, 4)

@@ -106,7 +106,7 @@ def test_softmax_bwd_upsample_sum_transpose(dtype):
                                           ("up_blocks.2.resnets.0.conv_shortcut", 512, 256)])
 def test_conv_input_gradient(dtype, pre, cin, cout):
     """conv(gy, WeightCache.conv_dgrad(...)) vs autograd's grad_input of F.conv2d(padding=1) / the 1x1 shortcut"""
-    from cvvae_amd import _lib as L, grad, ops
+    from cvvae_amd import _lib as L, backward, ops
     from cvvae_amd.engine import P2D, ZERO
     m, sd = decoder(dtype)
     wc = m._cache()
@@ -117,15 +117,15 @@ def test_conv_input_gradient(dtype, pre, cin, cout):
     gy = torch.randn(N, cout, H, W).to(dtype).float()
     F.conv2d(x, w, None, padding=w.shape[-1] // 2).backward(gy)
     if w.shape[-1] == 1:
-        got = nchw(grad._dgrad1x1(wc, ndhwc(gy, dtype), pre))
+        got = nchw(backward.dgrad1x1(wc, ndhwc(gy, dtype), pre))
     elif cout == 3:  # channel-padded cotangent, as the decoder's backward feeds it
         g = torch.zeros(N, 1, H, W, 32, dtype=dtype, device="cuda")
         g[..., :3] = ndhwc(gy, dtype)
-        got = nchw(grad._dgrad3x3(wc, g, pre, cin_pad=32))
+        got = nchw(backward.conv_dgrad(wc, g, pre, (1, 3, 3), P2D, cin_pad=32))
     elif cin == 16:  # NCDHW store of the narrow latent gradient
         got = ops.conv(ndhwc(gy, dtype), wc.conv_dgrad(pre, (1, 3, 3)), pad=P2D, pad_mode_hw=ZERO, out_mode=L.OUT_NCDHW)[:, :, 0].float().cpu()
     else:
-        got = nchw(grad._dgrad3x3(wc, ndhwc(gy, dtype), pre))
+        got = nchw(backward.conv_dgrad(wc, ndhwc(gy, dtype), pre, (1, 3, 3), P2D))
     e = rel(got, x.grad)
     print(f"\n[dgrad {pre} {str(dtype)[6:]}] rel {e:.2e}")
     assert e <= OP_TOL[dtype]
