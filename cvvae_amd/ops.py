@@ -6,6 +6,7 @@ from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import ctypes
+import math
 import os
 
 import torch
@@ -53,8 +54,21 @@ def _wscale(w: torch.Tensor) -> float:
     m = float(w.detach().abs().max())
     if not (m > 0.0) or m != m or m == float("inf"):
         return 1.0
-    import math
-    return float(2.0 ** (9 - math.floor(math.log2(m)) ))
+    return float(2.0 ** (9 - math.floor(math.log2(m))))
+
+
+def _scaled(w: torch.Tensor, ws: Optional[float] = None) -> Tuple[torch.Tensor, float]:
+    """(w * ws, ws) with ws the power-of-two pack scale of w (_wscale), or the caller's for an fp32 weight"""
+    ws = _wscale(w) if (ws is None or w.dtype != torch.float32) else float(ws)
+    return (w * ws if ws != 1.0 else w), ws
+
+
+def _bias(bias: Optional[torch.Tensor], cout: int, device) -> torch.Tensor:
+    """the fp32 bias a conv launch reads, padded with zeros to a multiple of 32 channels"""
+    b = torch.zeros(round_up(cout, 32), dtype=torch.float32, device=device)
+    if bias is not None:
+        b[:cout] = bias.detach().to(torch.float32)
+    return b
 
 
 def _stream(t: torch.Tensor) -> int:
@@ -122,18 +136,13 @@ def pack_weight(w: torch.Tensor, bias: Optional[torch.Tensor], k: Tuple[int, int
         out = torch.zeros(nbytes, dtype=torch.uint8, device=w.device)
     assert out.numel() * out.element_size() >= nbytes
     # wscale (fp32 weights only): force the power-of-two pack scale, e.g. the scale of the conv a fused shortcut accumulates with
-    ws = _wscale(w) if (wscale is None or w.dtype != torch.float32) else float(wscale)
-    if ws != 1.0:
-        w = w * ws
+    w, ws = _scaled(w, wscale)
     # fold = (n, stride): every packed element is the sum of n source elements `stride` apart (coinciding taps);
     # offset: element offset of the first source element (e.g. the centre time tap)
     L.check(lib.cvvae_pack_weights_fold(dt, w.data_ptr() + offset * w.element_size(), cout_, cin_, taps, strides[0],
                                         strides[1], strides[2], fold[0], fold[1], cin_pad, ck, out.data_ptr(), _stream(w)),
             "cvvae_pack_weights_fold")
-    b = torch.zeros(round_up(cout_, 32), dtype=torch.float32, device=w.device)
-    if bias is not None:
-        b[:cout_] = bias.detach().to(torch.float32)
-    return PackedConv(out, b, cout_, cin_pad, tuple(k), cin_, wscale=ws, dt=dt)
+    return PackedConv(out, _bias(bias, cout_, w.device), cout_, cin_pad, tuple(k), cin_, wscale=ws, dt=dt)
 
 
 def ncdhw_to_rowpack(x: torch.Tensor, dtype: torch.dtype, pad_mode_w: int) -> torch.Tensor:
@@ -235,8 +244,7 @@ def pack_weight_batched(w: torch.Tensor, k: Tuple[int, int, int], cin_pad: int, 
     L.check(lib.cvvae_pack_weights_batched(dt, w.data_ptr(), batch, w[0].numel(), cout, cin, taps, strides[0], strides[1],
                                            strides[2], cin_pad, kchunk(k), out.data_ptr(), per, _stream(w)),
             "cvvae_pack_weights_batched")
-    b = torch.zeros(round_up(cout, 32), dtype=torch.float32, device=w.device)
-    return PackedConv(out, b, cout, cin_pad, tuple(k), cin, batch_stride=per)
+    return PackedConv(out, _bias(None, cout, w.device), cout, cin_pad, tuple(k), cin, batch_stride=per)
 
 
 def pack_weight_tfolds(w: torch.Tensor, bias: Optional[torch.Tensor], cin_pad: Optional[int] = None, fast: bool = False) -> PackedConv:
@@ -253,15 +261,10 @@ def pack_weight_tfolds(w: torch.Tensor, bias: Optional[torch.Tensor], cin_pad: O
     ck = kchunk(k)
     cin_pad = round_up(ci, ck) if cin_pad is None else cin_pad
     out = torch.zeros(lib.cvvae_packed_weight_bytes(co, cin_pad, 6 * nsp * _xpm(w.dtype)), dtype=torch.uint8, device=w.device)
-    ws = _wscale(w)
-    if ws != 1.0:
-        w = w * ws
+    w, ws = _scaled(w)
     L.check(lib.cvvae_pack_weights_tfolds(dt, w.data_ptr(), co, ci, nsp, ci * 3 * nsp, 3 * nsp, 1, cin_pad, ck, out.data_ptr(),
                                           _stream(w)), "cvvae_pack_weights_tfolds")
-    b = torch.zeros(round_up(co, 32), dtype=torch.float32, device=w.device)
-    if bias is not None:
-        b[:co] = bias.detach().to(torch.float32)
-    return PackedConv(out, b, co, cin_pad, k, ci, time_folds=True, wscale=ws, dt=dt)
+    return PackedConv(out, _bias(bias, co, w.device), co, cin_pad, k, ci, time_folds=True, wscale=ws, dt=dt)
 
 
 def pack_weight_t1(w: torch.Tensor, bias: Optional[torch.Tensor], mode: str, cin_pad: Optional[int] = None,
@@ -292,20 +295,15 @@ def pack_weight_upfold(w: torch.Tensor, bias: Optional[torch.Tensor], tfold: int
     assert not (tfold and time_folds)
     per = lib.cvvae_packed_weight_bytes(cout_, cin_pad, (24 if time_folds else (4 if tfold else 12)) * _xpm(w.dtype))
     out = torch.zeros(4 * per, dtype=torch.uint8, device=w.device)
-    ws = _wscale(w)
-    if ws != 1.0:
-        w = w * ws
+    w, ws = _scaled(w)
     if time_folds:  # 12 taps per phase + the time-fold slots (replicate time padding)
         L.check(lib.cvvae_pack_weights_upfold_tfolds(dt, w.data_ptr(), cout_, cin_, cin_pad, out.data_ptr(), _stream(w)),
                 "cvvae_pack_weights_upfold_tfolds")
     else:
         L.check(lib.cvvae_pack_weights_upfold(dt, w.data_ptr(), cout_, cin_, cin_pad, tfold, out.data_ptr(), _stream(w)),
                 "cvvae_pack_weights_upfold")
-    b = torch.zeros(round_up(cout_, 32), dtype=torch.float32, device=w.device)
-    if bias is not None:
-        b[:cout_] = bias.detach().to(torch.float32)
-    return PackedConv(out, b, cout_, cin_pad, (1, 3, 3) if tfold else (3, 3, 3), cin_, folded=True, alg_taps=27,
-                      time_folds=time_folds, wscale=ws, dt=dt)
+    return PackedConv(out, _bias(bias, cout_, w.device), cout_, cin_pad, (1, 3, 3) if tfold else (3, 3, 3), cin_, folded=True,
+                      alg_taps=27, time_folds=time_folds, wscale=ws, dt=dt)
 
 
 def conv(x: torch.Tensor, pw: PackedConv, *, stride=(1, 1, 1), pad=((0, 0), (0, 0), (0, 0)), pad_mode_t=L.PAD_ZERO,
