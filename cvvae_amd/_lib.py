@@ -68,6 +68,19 @@ class ReduceShape(ctypes.Structure):
     _fields_ = [("n", ctypes.c_int64 * 3), ("L", ctypes.c_int64), ("sa", ctypes.c_int64 * 3), ("sb", ctypes.c_int64 * 3)]
 
 
+FMAP_GATHER, FMAP_GROUP_MEAN = 0, 1  # cvvae_frame_map.mode
+FMAP_MAX_FRAMES = 256
+
+
+class FrameMap(ctypes.Structure):
+    """mirror of `cvvae_frame_map` (include/cvvae.h)"""
+
+    _fields_ = [("mode", ctypes.c_int32), ("group", ctypes.c_int32),
+                ("rows", ctypes.c_int64), ("frames_in", ctypes.c_int64), ("frames_out", ctypes.c_int64), ("HW", ctypes.c_int64),
+                ("row_stride", ctypes.c_int64), ("frame_stride", ctypes.c_int64),
+                ("index", ctypes.POINTER(ctypes.c_int32))]
+
+
 _vp, _i32, _i64, _f32, _f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 
 # name -> (restype, argtypes): every symbol include/cvvae.h declares
@@ -129,6 +142,9 @@ PROTOTYPES = {
     "cvvae_reduce_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(ReduceShape)]),
     "cvvae_reduce_sum": (_i32, [_i32, _i32, _vp, _i32, _vp, ctypes.POINTER(ReduceShape), _vp, _vp, _vp]),
     "cvvae_reduce_sum_bwd": (_i32, [_i32, _i32, _vp, _i32, _vp, ctypes.POINTER(ReduceShape), _vp, _vp, _vp, _vp]),
+    "cvvae_reduce_frames_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(FrameMap)]),
+    "cvvae_reduce_sum_frames": (_i32, [_i32, _i32, _vp, _i32, _vp, ctypes.POINTER(FrameMap), _vp, _vp, _vp]),
+    "cvvae_reduce_sum_frames_bwd": (_i32, [_i32, _i32, _vp, _i32, _vp, ctypes.POINTER(FrameMap), _vp, _vp, _vp]),
     "cvvae_gauss_reg": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "cvvae_gauss_reg_bwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     "cvvae_avgpool3d_down": (_i32, [_i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),

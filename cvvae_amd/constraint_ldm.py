@@ -6,8 +6,11 @@ AttnBlock in the middle, Downsample = zero pad right/bottom + 3x3 stride 2, Upsa
 clips are coded frame by frame ('b c t h w -> (b t) c h w'), with the `quant_conv` / `post_quant_conv` 1x1 layers of the legacy
 checkpoints.  The training engines hold them FROZEN (`self.constraint_encoder.requires_grad_(False)` under `torch.no_grad()`,
 lvdm/models/autoencoder.py:1271-1284: `z_d = self.constraint_encoder(x[:, :, ::time_n_compress])`).  Same constructor keywords,
-same state-dict names and shapes; forward only (no gradients: the reference calls the encoder under no_grad; the input gradient
-of a constraint DECODER exists for the SD3 one only, cvvae_amd/grad.py).
+same state-dict names and shapes.  The encoder is forward only (the reference calls it under no_grad).  The decoder is never
+trained either, but the latent-compatibility loss back-propagates THROUGH it into the 3-D encoder's latents
+(`xrec_2d = self.constraint_decoder(z)`): when its input requires grad (and autograd is enabled) the call is recorded as one
+autograd node whose backward is the frozen decoder's input gradient on the same kernels (cvvae_amd/grad.py,
+`ldm2d_decoder_backward`), as for the SD3 constraint decoder (cvvae_amd/constraint.py).  Weight gradients are not built.
 """
 from typing import Sequence
 
@@ -114,11 +117,24 @@ class Decoder(_Net):
         self.last_z_shape = None
         self._cfg = dict(ch_mult=list(ch_mult), num_res_blocks=num_res_blocks)
 
+    def _run(self, z: torch.Tensor) -> torch.Tensor:
+        """z [b,c,t,h,w] -> pixels; differentiable w.r.t. z when z requires grad (input gradient only: the module is frozen)"""
+        if torch.is_grad_enabled() and z.requires_grad:
+            self._check_input(z)
+            if any(p.requires_grad for p in self.parameters()):
+                raise NotImplementedError("only the frozen decoder's input gradient is built (the reference calls "
+                                          "constraint_decoder.requires_grad_(False)); weight gradients are not")
+            from .grad import LdmDecoderFn
+            from .modeling import _autocast_dtype
+            with self._cache().computing_in(_autocast_dtype(z) if self.conv_in.weight.dtype == torch.float32 else None):
+                return LdmDecoderFn.apply(z, self)
+        return _Net.forward(self, z)
+
     def forward(self, z: torch.Tensor, **kwargs) -> torch.Tensor:
         if z.dim() != 4:
             raise ValueError(f"expected a [N,C,H,W] tensor, got shape {tuple(z.shape)}")
         self.last_z_shape = z.shape
-        return _Net.forward(self, z.unsqueeze(2)).squeeze(2)
+        return self._run(z.unsqueeze(2)).squeeze(2)
 
 
 class EncoderWith3DWrapper(Encoder):
@@ -146,5 +162,5 @@ class DecoderWith3DWrapper(Decoder):
     def forward(self, z: torch.Tensor, **kwargs) -> torch.Tensor:
         if z.dim() == 5:
             self.last_z_shape = z.shape
-            return _Net.forward(self, z)
+            return self._run(z)
         return super().forward(z)

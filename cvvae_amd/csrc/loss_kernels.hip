@@ -1,5 +1,6 @@
 // loss_kernels.hip -- the passes of the training loss around the networks (cvvae_amd/loss.py): a deterministic map-reduce to one
-// fp32 scalar (pixel terms, KL, the GAN terms, the gradient norms of the adaptive weight), its adjoint, and the diagonal-Gaussian
+// fp32 scalar (pixel terms, KL, the GAN terms, the gradient norms of the adaptive weight), its adjoint, the same pair with a
+// frame-mapped second operand (the "random" / "mean" 2-D targets of the constraint losses), and the diagonal-Gaussian
 // posterior (sample + KL) forward and backward.  gfx950 only.  All of them are HBM- or latency-bound: plain C++.
 //
 // Order of summation.  Elements are numbered by their LOGICAL index i (outer dimensions slowest, the inner run fastest).  Group
@@ -146,6 +147,105 @@ __global__ __launch_bounds__(WG) void reduce_bwd_kernel(int op, const TA* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Frame-mapped second operand (cvvae_frame_map): the 2-D target of the constraint losses, rows x frames_out x HW, whose frame t'
+// is a frame of the clip picked through a table (GATHER) or the mean of `group` consecutive frames (GROUP_MEAN) -- read from the
+// clip in place.  The table travels in the kernel arguments.  Same element numbering, grid and two stages as above, so the sum
+// carries the bits of cvvae_reduce_sum over the materialised target.
+// ---------------------------------------------------------------------------------------------------------
+struct FrameMap {
+  int mode, group;
+  long long frames_out, HW, row_stride, frame_stride;
+  float inv_group;
+  int index[CVVAE_FMAP_MAX_FRAMES];
+};
+
+// the n (<= 8) target values at position j of frame tf of row r; whole = the group lies inside this frame's run
+template <typename T>
+__device__ __forceinline__ void target_run(const T* __restrict__ clip, const FrameMap& m, long long r, long long tf, long long j, int n,
+                                           float (&f)[VEC]) {
+  const T* base = clip + r * m.row_stride + j;
+  if (m.mode == CVVAE_FMAP_GATHER) {
+    ld8_n<T>(base + (long long)m.index[tf] * m.frame_stride, n, f);
+    return;
+  }
+  if (tf == 0) {
+    ld8_n<T>(base, n, f);
+    return;
+  }
+  const long long s = 1 + (tf - 1) * m.group;
+  ld8_n<T>(base + s * m.frame_stride, n, f);
+  for (int q = 1; q < m.group; ++q) {
+    float c[VEC];
+    ld8_n<T>(base + (s + q) * m.frame_stride, n, c);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) f[k] += c[k];
+  }
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) f[k] = __fmul_rn(f[k], m.inv_group);  // (its own rounding: never contracted into the term's a - b)
+}
+
+// the target values of logical indices [i, i + n)
+template <typename T>
+__device__ __forceinline__ void target8(const T* __restrict__ clip, const FrameMap& m, long long i, int n, float (&f)[VEC]) {
+  const long long fr = i / m.HW, j = i - fr * m.HW;
+  if (n == VEC && j + VEC <= m.HW) {
+    const long long r = fr / m.frames_out;
+    target_run<T>(clip, m, r, fr - r * m.frames_out, j, VEC, f);
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) {
+    f[k] = 0.f;
+    if (k < n) {
+      const long long fk = (i + k) / m.HW, r = fk / m.frames_out;
+      float one[VEC];
+      target_run<T>(clip, m, r, fk - r * m.frames_out, (i + k) - fk * m.HW, 1, one);
+      f[k] = one[0];
+    }
+  }
+}
+
+template <typename TA, typename TB>
+__global__ __launch_bounds__(WG) void reduce_frames_partial_kernel(int op, const TA* __restrict__ a, const TB* __restrict__ clip,
+                                                                   const FrameMap m, long long total, float* __restrict__ ws) {
+  const long long ntiles = (total + TILE - 1) / TILE;
+  float acc = 0.f;
+  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const long long i = (t * WG + threadIdx.x) * VEC;
+    if (i >= total) continue;
+    const int n = (total - i) < VEC ? (int)(total - i) : VEC;
+    float fa[VEC], fb[VEC];
+    ld8_n<TA>(a + i, n, fa);
+    target8<TB>(clip, m, i, n, fb);
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) s += (k < n) ? term(op, fa[k], fb[k]) : 0.f;
+    acc += s;
+  }
+  acc = block_sum(acc);
+  if (threadIdx.x == 0) ws[blockIdx.x] = acc;
+}
+
+template <typename TA, typename TB>
+__global__ __launch_bounds__(WG) void reduce_frames_bwd_kernel(int op, const TA* __restrict__ a, const TB* __restrict__ clip,
+                                                               const FrameMap m, long long total, const float* __restrict__ coef_dev,
+                                                               TA* __restrict__ ga) {
+  const float coef = coef_dev[0];
+  const long long ntiles = (total + TILE - 1) / TILE;
+  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const long long i = (t * WG + threadIdx.x) * VEC;
+    if (i >= total) continue;
+    const int n = (total - i) < VEC ? (int)(total - i) : VEC;
+    float fa[VEC], fb[VEC], g[VEC];
+    ld8_n<TA>(a + i, n, fa);
+    target8<TB>(clip, m, i, n, fb);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) g[k] = coef * term_grad(op, fa[k], fb[k]);
+    st8_n<TA>(ga + i, g, n);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // DiagonalGaussianDistribution (lvdm/modules/distributions/distributions.py:24-52) in one pass: moments [B][2C][S] chunked at
 // channel C into mean and logvar, logvar clamped to [-30, 20], z = mean + exp(0.5 logvar) * noise (noise NULL: z = mean), and the
 // partial sums of mean^2 + var - 1 - logvar.  Rows are the B samples, the inner run the C * S values of one chunk.
@@ -247,6 +347,41 @@ static inline long long shape_total(const cvvae_reduce_shape* s, bool two) {
 static inline bool known_op(int32_t op) { return op >= CVVAE_RED_ABS_DIFF && op <= CVVAE_RED_SOFTPLUS_POS; }
 static inline bool two_operands(int32_t op) { return op == CVVAE_RED_ABS_DIFF || op == CVVAE_RED_SQ_DIFF; }
 
+// a frame map as the kernels take it -> 0 and the element count of the target, or the status to return (nothing was launched)
+static inline int frame_map_args(const cvvae_frame_map* fm, FrameMap* m, long long* total) {
+  if (!fm) return CVVAE_EINVAL;
+  if (fm->mode != CVVAE_FMAP_GATHER && fm->mode != CVVAE_FMAP_GROUP_MEAN) return CVVAE_EINVAL;
+  if (fm->rows <= 0 || fm->frames_in <= 0 || fm->frames_out <= 0 || fm->HW <= 0) return CVVAE_EINVAL;
+  if (fm->frames_out > CVVAE_FMAP_MAX_FRAMES) return CVVAE_EUNSUPPORTED;
+  // a stride of a dimension of extent 1 is never multiplied by anything but 0
+  if (fm->frames_in > 1 && fm->frame_stride < fm->HW) return CVVAE_EINVAL;
+  if (fm->HW > (1LL << 40) / fm->frames_in || fm->frame_stride > (1LL << 40) / fm->frames_in) return CVVAE_EUNSUPPORTED;
+  if (fm->rows > 1 && fm->row_stride < (fm->frames_in - 1) * fm->frame_stride + fm->HW) return CVVAE_EINVAL;
+  if (fm->rows > 1 && fm->row_stride > (1LL << 40) / fm->rows) return CVVAE_EUNSUPPORTED;
+  if (fm->frames_out * fm->HW > (1LL << 40) / fm->rows) return CVVAE_EUNSUPPORTED;
+  m->mode = fm->mode;
+  m->group = 1;
+  m->inv_group = 1.0f;
+  if (fm->mode == CVVAE_FMAP_GATHER) {
+    if (!fm->index) return CVVAE_EINVAL;
+    for (long long t = 0; t < fm->frames_out; ++t) {
+      if (fm->index[t] < 0 || fm->index[t] >= fm->frames_in) return CVVAE_EINVAL;
+      m->index[t] = fm->index[t];
+    }
+  } else {
+    if (fm->group < 1 || fm->frames_in != 1 + (fm->frames_out - 1) * (long long)fm->group) return CVVAE_EINVAL;
+    m->group = fm->group;
+    m->inv_group = 1.0f / (float)fm->group;
+  }
+  m->frames_out = fm->frames_out;
+  m->HW = fm->HW;
+  m->row_stride = fm->rows > 1 ? fm->row_stride : 0;
+  m->frame_stride = fm->frames_in > 1 ? fm->frame_stride : 0;
+  *total = fm->rows * fm->frames_out * fm->HW;
+  return 0;
+}
+static inline bool frames_op(int32_t op) { return two_operands(op); }
+
 }  // namespace loss
 }  // namespace cvvae
 
@@ -308,6 +443,57 @@ int cvvae_reduce_sum_bwd(int32_t op, int32_t dtype_a, const void* a, int32_t dty
       using TB = typename decltype(tb)::type;
       hipLaunchKernelGGL((reduce_bwd_kernel<TA, TB>), dim3(nblk), dim3(WG), 0, s, op, (const TA*)a, va, (const TB*)b, vb, total, coef_dev,
                          (TA*)ga, (TB*)gb);
+    });
+  });
+  return launch_status();
+}
+
+size_t cvvae_reduce_frames_workspace_bytes(const cvvae_frame_map* map) {
+  FrameMap m{};
+  long long total = 0;
+  if (frame_map_args(map, &m, &total) != 0) return 0;
+  return (size_t)blocks_for(total) * sizeof(float);
+}
+
+int cvvae_reduce_sum_frames(int32_t op, int32_t dtype_a, const void* a, int32_t dtype_b, const void* clip, const cvvae_frame_map* map,
+                            void* workspace, float* out, void* stream) {
+  if (!a || !clip || !map || !workspace || !out) return CVVAE_EINVAL;
+  if (!frames_op(op) || !known_dtype(dtype_a) || !known_dtype(dtype_b)) return CVVAE_EUNSUPPORTED;
+  FrameMap m{};
+  long long total = 0;
+  const int rc = frame_map_args(map, &m, &total);
+  if (rc != 0) return rc;
+  const int nblk = (int)blocks_for(total);
+  hipStream_t s = (hipStream_t)stream;
+  by_dtype(dtype_a, [&](auto ta) {
+    by_dtype(dtype_b, [&](auto tb) {
+      using TA = typename decltype(ta)::type;
+      using TB = typename decltype(tb)::type;
+      hipLaunchKernelGGL((reduce_frames_partial_kernel<TA, TB>), dim3(nblk), dim3(WG), 0, s, op, (const TA*)a, (const TB*)clip, m, total,
+                         (float*)workspace);
+    });
+  });
+  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(WG), 0, s, (const float*)workspace, nblk, 1.0f, out);
+  return launch_status();
+}
+
+int cvvae_reduce_sum_frames_bwd(int32_t op, int32_t dtype_a, const void* a, int32_t dtype_b, const void* clip, const cvvae_frame_map* map,
+                                const float* coef_dev, void* ga, void* stream) {
+  if (!a || !clip || !map || !coef_dev || !ga) return CVVAE_EINVAL;
+  if (!frames_op(op) || !known_dtype(dtype_a) || !known_dtype(dtype_b)) return CVVAE_EUNSUPPORTED;
+  FrameMap m{};
+  long long total = 0;
+  const int rc = frame_map_args(map, &m, &total);
+  if (rc != 0) return rc;
+  const long long tiles = (total + TILE - 1) / TILE;
+  const int nblk = (int)(tiles < 65536 ? tiles : 65536);
+  hipStream_t s = (hipStream_t)stream;
+  by_dtype(dtype_a, [&](auto ta) {
+    by_dtype(dtype_b, [&](auto tb) {
+      using TA = typename decltype(ta)::type;
+      using TB = typename decltype(tb)::type;
+      hipLaunchKernelGGL((reduce_frames_bwd_kernel<TA, TB>), dim3(nblk), dim3(WG), 0, s, op, (const TA*)a, (const TB*)clip, m, total,
+                         coef_dev, (TA*)ga);
     });
   });
   return launch_status();

@@ -844,30 +844,37 @@ def ldm2d_encoder(wc: WeightCache, x: torch.Tensor, cfg: dict) -> torch.Tensor:
     return _frames_out(m, B, T)
 
 
-def ldm2d_decoder(wc: WeightCache, z: torch.Tensor, cfg: dict) -> torch.Tensor:
+def ldm2d_decoder(wc: WeightCache, z: torch.Tensor, cfg: dict, tape: Optional[list] = None) -> torch.Tensor:
     """DecoderWith3DWrapper.forward over Decoder.forward (model.py:728-772, 820-830): post_quant_conv 1x1 -> conv_in -> mid ->
     levels (num_res_blocks + 1 ResnetBlocks, Upsample = nearest x2 + 3x3) from the coarsest -> norm_out + swish + conv_out.
-    z NCDHW [b,zc,t,h,w] -> pixels [b,out_ch,t,f*h,f*w]."""
+    z NCDHW [b,zc,t,h,w] -> pixels [b,out_ch,t,f*h,f*w].  tape: a list that receives what the input-gradient pass of the frozen
+    decoder (grad.ldm2d_decoder_backward) reads again; None (inference): the launches are exactly those of the untaped pass."""
     dtype = wc.p("conv_in.weight").dtype
-    B, T = z.shape[0], z.shape[2]
+    B, zin, T = z.shape[0], z.shape[1], z.shape[2]
     nlev = len(cfg["ch_mult"])
-    if wc.has("post_quant_conv.weight"):
+    pqc = wc.has("post_quant_conv.weight")
+    if pqc:
         h = _frames_in(z, 128, dtype)
         pq = wc.conv("post_quant_conv", (1, 1, 1), cin_pad=128)
         h = ops.conv(_flat(h), pq, cout_pad=32).view(*h.shape[:-1], 32)
     else:
         h = _frames_in(z, 32, dtype)
     h, hp = ops.conv(h, wc.conv("conv_in", (1, 3, 3), cin_pad=32), pad=P2D, pad_mode_hw=ZERO, gn_out=G32)
-    h, hp = c2d_resnet(wc, h, hp, "mid.block_1", sc=".nin_shortcut")
+    h, hp = c2d_resnet(wc, h, hp, "mid.block_1", sc=".nin_shortcut", tape=tape)
     a = "mid.attn_1"
-    h, hp = spatial_attention(wc, h, a + ".norm", a + ".q", a + ".k", a + ".v", a + ".proj_out", 1e-6, True, gn_out=G32, xp=hp)
-    h, hp = c2d_resnet(wc, h, hp, "mid.block_2", sc=".nin_shortcut")
+    h, hp = spatial_attention(wc, h, a + ".norm", a + ".q", a + ".k", a + ".v", a + ".proj_out", 1e-6, True, gn_out=G32, xp=hp,
+                              tape=tape)
+    h, hp = c2d_resnet(wc, h, hp, "mid.block_2", sc=".nin_shortcut", tape=tape)
     for lvl in reversed(range(nlev)):
         for j in range(cfg["num_res_blocks"] + 1):
-            h, hp = c2d_resnet(wc, h, hp, f"up.{lvl}.block.{j}", sc=".nin_shortcut")
+            h, hp = c2d_resnet(wc, h, hp, f"up.{lvl}.block.{j}", sc=".nin_shortcut", tape=tape)
         if lvl != 0:  # Upsample: nearest x2 + conv 3x3 pad 1 (model.py:68-75), as four folded 1x2x2 phase convs
+            if tape is not None:
+                tape.append(dict(op="up", pre=f"up.{lvl}.upsample.conv"))
             h, hp = ops.conv(h, wc.conv_upfold2d(f"up.{lvl}.upsample.conv"), pad=P2D, pad_mode_hw=ZERO, upsample2x=2, gn_out=G32)
     g = _norm(wc, h, hp, "norm_out", 1e-6)
+    if tape is not None:
+        tape.append(dict(op="out", x=h, xp=hp, B=B, T=T, zin=zin, post_quant_conv=pqc))
     y = ops.conv(h, wc.conv("conv_out", (1, 3, 3)), pad=P2D, pad_mode_hw=ZERO, prologue=L.PRO_GN_SILU, gn=g, out_mode=L.OUT_NCDHW)
     return _frames_out(y, B, T)
 

@@ -117,3 +117,66 @@ class ConstraintDecoderFn(torch.autograd.Function):
         with backward_pass(ctx, gy):
             gz = constraint_decoder2d_backward(ctx.net._cache(), ctx.tape, gy)
         return node_grads(ctx, gz, 1, None)
+
+
+# --------------------------------------------------------------------------------------------------------
+# the frozen LDM (SD2.1-family) image decoder: the same pass over engine.ldm2d_decoder's tape
+# --------------------------------------------------------------------------------------------------------
+def ldm2d_decoder_backward(wc: WeightCache, tape: List[dict], gy: torch.Tensor) -> torch.Tensor:
+    """gy = dL/d(output) [b,out_ch,t,H,W] of engine.ldm2d_decoder(wc, z, cfg, tape) -> dL/dz [b,zc,t,h,w].  Decoder.forward of
+    lvdm/modules/diffusionmodules/model.py:728-772 backwards: conv_out, norm_out + swish, the levels (ResnetBlocks with 1x1
+    nin_shortcut, Upsample = nearest x2 + 3x3), mid (block_2, attn_1, block_1), conv_in and -- legacy=True -- post_quant_conv."""
+    dtype = wc.p("conv_in.weight").dtype
+    last = tape[-1]
+    assert last["op"] == "out"
+    B, T, zin = last["B"], last["T"], last["zin"]
+    out_ch = wc.p("conv_out.weight").shape[0]
+    if tuple(gy.shape[:3]) != (B, out_ch, T) or out_ch > 32:
+        raise NotImplementedError(f"ldm2d_decoder_backward: cotangent {tuple(gy.shape)} for a decoder with {out_ch} <= 32 output "
+                                  f"channels over {B} x {T} frames")
+    g = ops.ncdhw_to_ndhwc(gy.contiguous(), 32, dtype)                                           # [b,t,H,W,32], channels out_ch.. zero
+    g = g.view(B * T, 1, g.shape[2], g.shape[3], 32)
+    g = conv_dgrad(wc, g, "conv_out", K2D, P2D, cin_pad=32)                                      # dL/d swish(norm_out(h))
+    x = last["x"]
+    g = ops.gn_bwd_input(x, g, unit_tabs(x, last["xp"], 1e-6), *wc.norm("norm_out"), silu=True)
+    for e in reversed(tape[:-1]):
+        if e["op"] == "resnet":
+            pre = e["pre"] + "."
+            g = backward.resnet_backward(wc, g, None, block_names(wc, pre, "nin_shortcut"), e["x"], e["xp"], e["h"], e["hp"], 1e-6,
+                                         conv1=(K2D, {}), conv2=(K2D, P2D),
+                                         dgrad1=lambda gh, pre=pre: conv_dgrad(wc, gh, pre + "conv1", K2D, P2D))
+        elif e["op"] == "attn":
+            g = attention_backward(wc, g, e)
+        elif e["op"] == "up":  # Upsample: nearest x2, then conv 3x3
+            g = ops.upsample2x_sum(conv_dgrad(wc, g, e["pre"], K2D, P2D))
+        else:
+            raise AssertionError(e["op"])
+    if not last["post_quant_conv"]:
+        gz = conv_dgrad(wc, g, "conv_in", K2D, P2D, out_mode=L.OUT_NCDHW)                        # [b*t, zin, 1, h, w]
+    else:
+        # conv_in's input gradient keeps the pixel-major layout, channel-padded to the 1x1 kernel's K chunk as the forward pads the
+        # latents; post_quant_conv (zin -> zin) backwards on the flattened pixels; then the narrow gradient goes to NCDHW
+        if zin > 32:
+            raise NotImplementedError(f"ldm2d_decoder_backward: post_quant_conv with {zin} > 32 channels")
+        g = conv_dgrad(wc, g, "conv_in", K2D, P2D, cout_pad=128)                                 # [b*t,1,h,w,128]
+        pq = wc.conv_dgrad("post_quant_conv", K1, cin_pad=128)
+        g = ops.conv(engine._flat(g), pq, cout_pad=32).view(*g.shape[:-1], 32)
+        gz = ops.ndhwc_to_ncdhw(g, zin)
+    return gz.view(B, T, zin, gz.shape[3], gz.shape[4]).transpose(1, 2).contiguous()
+
+
+class LdmDecoderFn(torch.autograd.Function):
+    """z -> the frozen LDM Decoder(z) with its input gradient as backward (both on the HIP kernels)"""
+
+    @staticmethod
+    def forward(ctx, z: torch.Tensor, net) -> torch.Tensor:
+        y, ctx.tape = taped(z, lambda tape: engine.ldm2d_decoder(net._cache(), z.detach(), net._cfg, tape))
+        begin_node(ctx, net, z, cd=net._cache().compute_dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        # (the tape lives as long as the node: a second backward under retain_graph=True walks it again and gives the same bits)
+        with backward_pass(ctx, gy):
+            gz = ldm2d_decoder_backward(ctx.net._cache(), ctx.tape, gy)
+        return node_grads(ctx, gz, 1, None)

@@ -1083,6 +1083,67 @@ def reduce_sum_bwd(op: int, a: torch.Tensor, b: Optional[torch.Tensor], coef: to
     return ga, gb
 
 
+def _frame_map(op: int, a: torch.Tensor, clip: torch.Tensor, mode: int, index, group) -> "L.FrameMap":
+    """a [B,C,T',H,W] contiguous and the clip [B,C,T,H,W] it is compared with through a frame map, as cvvae_frame_map.  The clip is
+    read in place: its H, W must be one contiguous run and B, C must merge into one row stride (a `[:, :, :, 1:-1]` view does)."""
+    _need_gpu(a)
+    _need_gpu(clip)
+    if op not in TWO_OPERAND_OPS:
+        raise ValueError(f"cvvae_reduce_sum_frames op {op}: ABS_DIFF / SQ_DIFF only")
+    if a.dim() != 5 or clip.dim() != 5 or a.shape[:2] != clip.shape[:2] or a.shape[3:] != clip.shape[3:] or a.device != clip.device:
+        raise ValueError(f"cvvae_reduce_sum_frames: a [B,C,T',H,W] and clip [B,C,T,H,W] on one device; got {tuple(a.shape)} and "
+                         f"{tuple(clip.shape)}")
+    if a.numel() == 0 or clip.numel() == 0:
+        raise ValueError("cvvae_reduce_sum_frames: empty tensor")
+    if not a.is_contiguous():
+        raise ValueError("cvvae_reduce_sum_frames: a must be contiguous")
+    B, C, T, H, W = clip.shape
+    sb, sc, st, sh, sw = clip.stride()
+    if (W > 1 and sw != 1) or (H > 1 and sh != W) or (B > 1 and C > 1 and sb != C * sc) or min(sb, sc, st) < 0:
+        raise ValueError(f"cvvae_reduce_sum_frames reads a clip whose H, W are contiguous and whose B, C merge into one row stride; got "
+                         f"sizes {tuple(clip.shape)} with strides {tuple(clip.stride())}")
+    m = L.FrameMap()
+    m.mode, m.group = mode, 1
+    m.rows, m.frames_in, m.frames_out, m.HW = B * C, T, a.shape[2], H * W
+    m.row_stride, m.frame_stride = (sc if C > 1 else sb), st
+    if mode == L.FMAP_GATHER:
+        idx = [int(i) for i in (index.tolist() if isinstance(index, torch.Tensor) else index)]
+        if len(idx) != a.shape[2]:
+            raise ValueError(f"cvvae_reduce_sum_frames: {len(idx)} frame indices for {a.shape[2]} target frames")
+        m._index = (ctypes.c_int32 * len(idx))(*idx)  # (kept alive by the struct object)
+        m.index = ctypes.cast(m._index, ctypes.POINTER(ctypes.c_int32))
+    elif mode == L.FMAP_GROUP_MEAN:
+        m.group = int(group)
+    else:
+        raise ValueError(f"cvvae_reduce_sum_frames: unknown mode {mode}")
+    return m
+
+
+def reduce_sum_frames(op: int, a: torch.Tensor, clip: torch.Tensor, mode: int, *, index=None, group=None) -> torch.Tensor:
+    """sum f_op(a, target) -> 0-dim fp32, target [B,C,T',H,W] being frames of `clip` [B,C,T,H,W] read in place: mode L.FMAP_GATHER
+    takes frame index[t'] (HOST ints: a list or a CPU tensor), L.FMAP_GROUP_MEAN frame 0 and then the fp32 means of `group`
+    consecutive frames.  The bits of reduce_sum(op, a, materialised target)."""
+    lib = L.load()
+    m = _frame_map(op, a, clip, mode, index, group)
+    ws = torch.empty(max(int(lib.cvvae_reduce_frames_workspace_bytes(ctypes.byref(m))), 16), dtype=torch.uint8, device=a.device)
+    out = torch.empty((), dtype=torch.float32, device=a.device)
+    L.check(lib.cvvae_reduce_sum_frames(op, _dt(a.dtype), a.data_ptr(), _dt(clip.dtype), clip.data_ptr(), ctypes.byref(m), ws.data_ptr(),
+                                        out.data_ptr(), _stream(a)), "cvvae_reduce_sum_frames")
+    return out
+
+
+def reduce_sum_frames_bwd(op: int, a: torch.Tensor, clip: torch.Tensor, coef: torch.Tensor, mode: int, *, index=None,
+                          group=None) -> torch.Tensor:
+    """-> ga = coef * f_op'(a, target), shaped as a in its dtype; coef: a 0-dim fp32 DEVICE tensor.  The clip gets no gradient."""
+    lib = L.load()
+    m = _frame_map(op, a, clip, mode, index, group)
+    assert coef.dtype == torch.float32 and coef.numel() == 1 and coef.device == a.device
+    ga = torch.empty(a.shape, dtype=a.dtype, device=a.device)
+    L.check(lib.cvvae_reduce_sum_frames_bwd(op, _dt(a.dtype), a.data_ptr(), _dt(clip.dtype), clip.data_ptr(), ctypes.byref(m),
+                                            coef.data_ptr(), ga.data_ptr(), _stream(a)), "cvvae_reduce_sum_frames_bwd")
+    return ga
+
+
 def _gauss_dims(moments: torch.Tensor) -> Tuple[int, int, int]:
     _need_gpu(moments)
     if moments.dim() < 3 or moments.shape[1] % 2 or not moments.is_contiguous():

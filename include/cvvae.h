@@ -515,6 +515,36 @@ int cvvae_reduce_sum(int32_t op, int32_t dtype_a, const void* a, int32_t dtype_b
 int cvvae_reduce_sum_bwd(int32_t op, int32_t dtype_a, const void* a, int32_t dtype_b, const void* b, const cvvae_reduce_shape* shape,
                          const float* coef_dev, void* ga, void* gb, void* stream);
 /*
+ * Frame-mapped pixel sums: the 2-D target of the constraint losses (discriminator_loss.py target_type "random" / "mean") read from
+ * the clip in place.  Additions to ABI 14.  out[0] = sum_i f_op(a[i], target[i]), i the logical index of [rows][frames_out][HW];
+ * a (and ga) are contiguous in that shape; the clip is rows x frames_in runs of HW contiguous elements, frame (r, t) starting at
+ * element r row_stride + t frame_stride.
+ *   CVVAE_FMAP_GATHER      target[r, t', :] = clip[r, index[t'], :]; index: frames_out HOST ints in [0, frames_in), copied into the
+ *                          kernel arguments by the call (no device allocation, no copy, no synchronisation)
+ *   CVVAE_FMAP_GROUP_MEAN  target[r, 0, :] = clip[r, 0, :]; t' >= 1: (((c[s] + c[s+1]) + ...) + c[s+group-1]) * (1.0f / group) with
+ *                          s = 1 + (t' - 1) group, in fp32, left to right, one multiply; needs frames_in == 1 + (frames_out - 1) group
+ * op: CVVAE_RED_ABS_DIFF / CVVAE_RED_SQ_DIFF only, other ops (and dtypes, and frames_out > CVVAE_FMAP_MAX_FRAMES) are
+ * CVVAE_EUNSUPPORTED.  dtype_a / dtype_b (the clip's) as above.  The order of summation is cvvae_reduce_sum's over the same logical
+ * index -- same grid rule, same two stages, nothing atomic -- so the result carries the bits of cvvae_reduce_sum over the
+ * materialised target; workspace >= cvvae_reduce_frames_workspace_bytes (host code; 0 for a map that would be refused).
+ * CVVAE_EINVAL, before any launch: a NULL pointer (index too, for GATHER), a non-positive extent, group < 1, an index out of range,
+ * a frame_stride < HW or a row_stride smaller than the frames it spans (strides of extent-1 dimensions are not read).
+ * cvvae_reduce_sum_frames_bwd: ga[i] = coef f_op'(a[i], target[i]) in dtype_a, coef a DEVICE fp32 scalar.  The clip gets no gradient.
+ */
+enum { CVVAE_FMAP_GATHER = 0, CVVAE_FMAP_GROUP_MEAN = 1 };
+#define CVVAE_FMAP_MAX_FRAMES 256
+typedef struct cvvae_frame_map {
+  int32_t mode, group;                     /* GROUP_MEAN: frames averaged per target frame (>= 1) */
+  int64_t rows, frames_in, frames_out, HW; /* clip: rows x frames_in x HW;  a / ga: rows x frames_out x HW, contiguous */
+  int64_t row_stride, frame_stride;        /* element strides of the clip; its HW run is contiguous */
+  const int32_t* index;                    /* GATHER: frames_out HOST ints in [0, frames_in) */
+} cvvae_frame_map;
+size_t cvvae_reduce_frames_workspace_bytes(const cvvae_frame_map* map);
+int cvvae_reduce_sum_frames(int32_t op, int32_t dtype_a, const void* a, int32_t dtype_b, const void* clip, const cvvae_frame_map* map,
+                            void* workspace, float* out, void* stream);
+int cvvae_reduce_sum_frames_bwd(int32_t op, int32_t dtype_a, const void* a, int32_t dtype_b, const void* clip,
+                                const cvvae_frame_map* map, const float* coef_dev, void* ga, void* stream);
+/*
  * DiagonalGaussianDistribution (lvdm/modules/distributions/distributions.py:24-52) in one pass.  moments [B][2C][S] (S = t h w or
  * h w) is chunked at channel C into mean and logvar, logvar clamped to [-30, 20]; z [B][C][S] = mean + exp(0.5 logvar) noise
  * (noise [B][C][S], or NULL: z = mean); kl_sum[0] = 0.5 sum (mean^2 + exp(logvar) - 1 - logvar) over EVERYTHING, through the two-stage
