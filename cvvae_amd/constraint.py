@@ -7,6 +7,8 @@ latents to produce `xrec_2d` for the latent-compatibility loss (autoencoder.py:1
 Same constructor keywords, same state-dict names and shapes.  The decoder is never trained, but the loss back-propagates THROUGH
 it into the latents: when the input requires grad (and autograd is enabled) the call is recorded as one autograd node whose
 backward is the frozen decoder's input gradient on the same kernels (cvvae_amd/grad.py).  Weight gradients are not built.
+That route (`FrozenDecoder2D._run`) and the ResnetBlock holder are shared with the SD2.1 family's decoder (constraint_ldm.py): the
+two run one program of cvvae_amd/engine.py under two spellings of the layer names.
 """
 from typing import Tuple
 
@@ -17,14 +19,32 @@ from . import engine
 from .modeling import ConvP, NormP, _channel_constraints, _holder, _Net
 
 
-def _resnet2d(cin: int, cout: int) -> nn.Module:
+def _resnet2d(cin: int, cout: int, shortcut: str = "conv_shortcut") -> nn.Module:
+    """the ResnetBlock's parameters; `shortcut`: the family's name of the 1x1 conv of a block that changes the channel count"""
     m = _holder(norm1=NormP(cin), conv1=ConvP(cin, cout, (3, 3)), norm2=NormP(cout), conv2=ConvP(cout, cout, (3, 3)))
     if cin != cout:
-        m.add_module("conv_shortcut", ConvP(cin, cout, (1, 1)))
+        m.add_module(shortcut, ConvP(cin, cout, (1, 1)))
     return m
 
 
-class Decoder(_Net):
+class FrozenDecoder2D(_Net):
+    """what the frozen per-frame decoders of both families share (this file's and constraint_ldm.py's): the route into autograd"""
+
+    def _run(self, z: torch.Tensor) -> torch.Tensor:
+        """z [b,c,t,h,w] -> pixels; differentiable w.r.t. z when z requires grad (input gradient only: the module is frozen)"""
+        if torch.is_grad_enabled() and z.requires_grad:
+            self._check_input(z)
+            if any(p.requires_grad for p in self.parameters()):
+                raise NotImplementedError("only the frozen decoder's input gradient is built (the reference calls "
+                                          "constraint_decoder.requires_grad_(False)); weight gradients are not")
+            from .grad import Decoder2DInputGradFn
+            from .modeling import _autocast_dtype
+            with self._cache().computing_in(_autocast_dtype(z) if self.conv_in.weight.dtype == torch.float32 else None):
+                return Decoder2DInputGradFn.apply(z, self)
+        return _Net.forward(self, z)
+
+
+class Decoder(FrozenDecoder2D):
     """vae_models_sd3.py:196-362 (eval path).  `forward(sample)` takes [N, C, H, W]."""
 
     _program = staticmethod(engine.constraint_decoder2d)
@@ -64,19 +84,6 @@ class Decoder(_Net):
         self.gradient_checkpointing = True  # attribute of the reference class (vae_models_sd3.py:295); unused: forward only
         self._cfg = dict(block_out_channels=boc, layers_per_block=layers_per_block,
                          mid_block_add_attention=bool(mid_block_add_attention))
-
-    def _run(self, z: torch.Tensor) -> torch.Tensor:
-        """z [b,c,t,h,w] -> pixels; differentiable w.r.t. z when z requires grad (input gradient only: the module is frozen)"""
-        if torch.is_grad_enabled() and z.requires_grad:
-            self._check_input(z)
-            if any(p.requires_grad for p in self.parameters()):
-                raise NotImplementedError("only the frozen decoder's input gradient is built (the reference calls "
-                                          "constraint_decoder.requires_grad_(False)); weight gradients are not")
-            from .grad import ConstraintDecoderFn
-            from .modeling import _autocast_dtype
-            with self._cache().computing_in(_autocast_dtype(z) if self.conv_in.weight.dtype == torch.float32 else None):
-                return ConstraintDecoderFn.apply(z, self)
-        return _Net.forward(self, z)
 
     def forward(self, sample: torch.Tensor, latent_embeds=None) -> torch.Tensor:
         if latent_embeds is not None:

@@ -10,7 +10,8 @@ same state-dict names and shapes.  The encoder is forward only (the reference ca
 trained either, but the latent-compatibility loss back-propagates THROUGH it into the 3-D encoder's latents
 (`xrec_2d = self.constraint_decoder(z)`): when its input requires grad (and autograd is enabled) the call is recorded as one
 autograd node whose backward is the frozen decoder's input gradient on the same kernels (cvvae_amd/grad.py,
-`ldm2d_decoder_backward`), as for the SD3 constraint decoder (cvvae_amd/constraint.py).  Weight gradients are not built.
+`decoder2d_backward`): the route, the node and the walker are the SD3 constraint decoder's (`constraint.FrozenDecoder2D`), over the
+same engine program in the LDM spelling.  Weight gradients are not built.
 """
 from typing import Sequence
 
@@ -18,14 +19,8 @@ import torch
 import torch.nn as nn
 
 from . import engine
+from .constraint import FrozenDecoder2D, _resnet2d
 from .modeling import ConvP, NormP, _channel_constraints, _holder, _Net
-
-
-def _resblock(cin: int, cout: int) -> nn.Module:
-    m = _holder(norm1=NormP(cin), conv1=ConvP(cin, cout, (3, 3)), norm2=NormP(cout), conv2=ConvP(cout, cout, (3, 3)))
-    if cin != cout:
-        m.add_module("nin_shortcut", ConvP(cin, cout, (1, 1)))
-    return m
 
 
 def _attn(c: int) -> nn.Module:
@@ -62,13 +57,13 @@ class Encoder(_Net):
             bi, bo = ch * in_ch_mult[lvl], ch * ch_mult[lvl]
             blocks = nn.ModuleList()
             for _ in range(num_res_blocks):
-                blocks.append(_resblock(bi, bo))
+                blocks.append(_resnet2d(bi, bo, "nin_shortcut"))
                 bi = bo
             lv = _holder(block=blocks, attn=nn.ModuleList())
             if lvl != self.num_resolutions - 1:
                 lv.add_module("downsample", _holder(conv=ConvP(bi, bi, (3, 3))))
             self.down.append(lv)
-        self.mid = _holder(block_1=_resblock(bi, bi), attn_1=_attn(bi), block_2=_resblock(bi, bi))
+        self.mid = _holder(block_1=_resnet2d(bi, bi, "nin_shortcut"), attn_1=_attn(bi), block_2=_resnet2d(bi, bi, "nin_shortcut"))
         self.norm_out = NormP(bi)
         self.conv_out = ConvP(bi, 2 * z_channels if double_z else z_channels, (3, 3))
         self._cfg = dict(ch_mult=list(ch_mult), num_res_blocks=num_res_blocks)
@@ -79,7 +74,7 @@ class Encoder(_Net):
         return _Net.forward(self, x.unsqueeze(2)).squeeze(2)
 
 
-class Decoder(_Net):
+class Decoder(FrozenDecoder2D):
     """model.py:617-772."""
 
     _program = staticmethod(engine.ldm2d_decoder)
@@ -99,13 +94,13 @@ class Decoder(_Net):
         curr_res = resolution // 2 ** (self.num_resolutions - 1)
         self.z_shape = (1, z_channels, curr_res, curr_res)
         self.conv_in = ConvP(z_channels, bi, (3, 3))
-        self.mid = _holder(block_1=_resblock(bi, bi), attn_1=_attn(bi), block_2=_resblock(bi, bi))
+        self.mid = _holder(block_1=_resnet2d(bi, bi, "nin_shortcut"), attn_1=_attn(bi), block_2=_resnet2d(bi, bi, "nin_shortcut"))
         ups = [None] * self.num_resolutions
         for lvl in reversed(range(self.num_resolutions)):
             bo = ch * ch_mult[lvl]
             blocks = nn.ModuleList()
             for _ in range(num_res_blocks + 1):
-                blocks.append(_resblock(bi, bo))
+                blocks.append(_resnet2d(bi, bo, "nin_shortcut"))
                 bi = bo
             lv = _holder(block=blocks, attn=nn.ModuleList())
             if lvl != 0:
@@ -116,19 +111,6 @@ class Decoder(_Net):
         self.conv_out = ConvP(bi, out_ch, (3, 3))
         self.last_z_shape = None
         self._cfg = dict(ch_mult=list(ch_mult), num_res_blocks=num_res_blocks)
-
-    def _run(self, z: torch.Tensor) -> torch.Tensor:
-        """z [b,c,t,h,w] -> pixels; differentiable w.r.t. z when z requires grad (input gradient only: the module is frozen)"""
-        if torch.is_grad_enabled() and z.requires_grad:
-            self._check_input(z)
-            if any(p.requires_grad for p in self.parameters()):
-                raise NotImplementedError("only the frozen decoder's input gradient is built (the reference calls "
-                                          "constraint_decoder.requires_grad_(False)); weight gradients are not")
-            from .grad import LdmDecoderFn
-            from .modeling import _autocast_dtype
-            with self._cache().computing_in(_autocast_dtype(z) if self.conv_in.weight.dtype == torch.float32 else None):
-                return LdmDecoderFn.apply(z, self)
-        return _Net.forward(self, z)
 
     def forward(self, z: torch.Tensor, **kwargs) -> torch.Tensor:
         if z.dim() != 4:

@@ -3,10 +3,17 @@
 This is the host-side mirror of the reference's L1/L2 modules: every function names
 the reference forward it reproduces.  What the reference does as separate ATen ops (F.pad, F.interpolate,
 GroupNorm, SiLU, add, rearrange) is folded into the conv launches -- see include/cvvae.h.
+
+The networks themselves (the last third of the file) are ONE program per shape -- the ResnetBlock, the mid block, the per-frame 2-D
+decoder, the 3-D encoder and the 3-D decoder -- taking a `Spelling` (how the checkpoint names the layers: DIFFUSERS or LDM) and, in
+3-D, a `Geometry` (the family's padding rules: SD3_GEO or V3_GEO).  The entry points the modules run (`sd3_encoder`, `v3_decoder`,
+`constraint_decoder2d`, `ldm2d_decoder`, ...) are bindings of those to the shared programs.
 """
 import contextlib
+import dataclasses
+import functools
 import os
-from typing import Dict, Optional, Tuple
+from typing import Callable, Dict, Optional, Tuple
 
 import torch
 
@@ -662,144 +669,90 @@ def _encoder_input(x: torch.Tensor, cfg: dict, dtype: torch.dtype):
     return ops.ncdhw_to_ndhwc(x, cpad, dtype), cpad
 
 
+
 # --------------------------------------------------------------------------------------------------------
-# vae3d_sd3 family
+# The networks.  Every encoder / decoder here is the same U-shape -- conv_in, levels of ResnetBlocks with a down- or upsampling
+# conv between them, a mid block (ResnetBlock, attention, ResnetBlock), GroupNorm + SiLU + conv_out -- along two independent axes:
+#   * how the checkpoint SPELLS the layers: diffusers (vae3d_sd3 and the SD3 image decoder) or LDM (vae3d and the SD2.1 image VAE);
+#   * the GEOMETRY of the convs: per-frame 2-D with zero padding (the frozen image VAEs of the training path), or 3-D with a
+#     family's padding rules (Geometry).
+# One program per shape below; the entry points the modules name (modeling._Net._program) bind a spelling and a geometry to it.
 # --------------------------------------------------------------------------------------------------------
-def sd3_resnet(wc: WeightCache, x: torch.Tensor, xp, pre: str, causal: bool, want_stats: bool = True, tape: Optional[list] = None):
-    """ResnetBlock3D.forward, vae_blocks3d_sd3.py:517-569: GN(eps 1e-6)+SiLU fused into conv1 (replicate pad, causal
-    T(2,0) or (1,1)) and into conv2 (per-frame 3x3, zero pad); 1x1 shortcut; residual add in conv2's epilogue.
+@dataclasses.dataclass(frozen=True)
+class Spelling:
+    """the state-dict names of one family's layers ({i}: level / block index as it enters the name, {j}: ResnetBlock in the level)"""
+    name: str
+    down_block: str                 # ResnetBlock (i, j) going down ...
+    up_block: str                   # ... and going up
+    mid: Tuple[str, str]            # the mid block's two ResnetBlocks
+    attn: str                       # the mid block's attention ...
+    attn_names: Tuple[str, ...]     # ... and its norm, q, k, v, proj layers (full names, what spatial_attention takes)
+    shortcut: str                   # the ResnetBlock's 1x1 shortcut (with its leading dot)
+    down_conv: str
+    up_conv: str
+    norm_out: str
+    up_from_coarsest: bool          # up blocks are numbered from the coarsest one (0 first); False: by resolution level (0 last)
+    levels: str                     # cfg key whose length is the number of levels
+    blocks: str                     # cfg key: ResnetBlocks per level going down (one more going up)
+
+    def up_levels(self, n: int) -> range:
+        """the index that enters an up block's name, in the order the decoder visits them (coarsest first)"""
+        return range(n) if self.up_from_coarsest else range(n - 1, -1, -1)
+
+
+DIFFUSERS = Spelling(
+    "diffusers", "down_blocks.{i}.resnets.{j}", "up_blocks.{i}.resnets.{j}", ("mid_block.resnets.0", "mid_block.resnets.1"),
+    "mid_block.attentions.0", tuple("mid_block.attentions.0." + n for n in ("group_norm", "to_q", "to_k", "to_v", "to_out.0")),
+    ".conv_shortcut", "down_blocks.{i}.downsamplers.0.conv", "up_blocks.{i}.upsamplers.0.conv", "conv_norm_out", True,
+    "block_out_channels", "layers_per_block")
+LDM = Spelling(
+    "LDM", "down.{i}.block.{j}", "up.{i}.block.{j}", ("mid.block_1", "mid.block_2"),
+    "mid.attn_1", tuple("mid.attn_1." + n for n in ("norm", "q", "k", "v", "proj_out")),
+    ".nin_shortcut", "down.{i}.downsample.conv", "up.{i}.upsample.conv", "norm_out", False, "ch_mult", "num_res_blocks")
+
+
+def resnet(wc: WeightCache, x: torch.Tensor, xp, pre: str, want_stats: bool = True, tape: Optional[list] = None, *, eps: float,
+           conv1, sc: str):
+    """ResnetBlock of every family (vae_blocks3d_sd3.py:517-569, vae_models.py:390-410, vae_blocks_sd3.py:368-421, model.py:98-155):
+    GroupNorm + SiLU fused into conv1 and into conv2 (per-frame 3x3, zero pad), 1x1 shortcut `sc`, residual add in conv2's launch.
+    conv1: (pad, mode_t, mode_hw) of the family's 3x3x3 conv, or None = the per-frame 3x3 with zero padding on [frames,1,H,W,C].
     xp: GroupNorm partials of x from its producer (or None).  Returns (out, partials of out or None)."""
-    g1 = _norm(wc, x, xp, pre + ".norm1", 1e-6)
-    h, hp = conv3(wc, x, pre + ".conv1", pad=PC if causal else P1, pad_mode_t=REP, pad_mode_hw=REP,
-                     prologue=L.PRO_GN_SILU, gn=g1, gn_out=G32, act_norm=pre + ".norm1")
-    g2 = ops.gn_finalize(hp, *wc.norm(pre + ".norm2"), 1e-6)
-    if tape is not None:  # what the training-side backward (grad3d.py) reads again: block input, conv1 output, their statistics
-        tape.append(dict(op="resnet3d", pre=pre, x=x, xp=xp, h=h, hp=hp, g1=g1, g2=g2, pad=PC if causal else P1, mode_t=REP, mode_hw=REP,
-                         eps=1e-6, sc=".conv_shortcut"))
-    return resnet_tail(wc, x, h, pre, pre + ".conv_shortcut", g2, want_stats)
-
-
-def sd3_mid(wc: WeightCache, x: torch.Tensor, xp, pre: str, causal: bool, attention: bool, tape: Optional[list] = None):
-    """UNetMidBlock3D.forward, vae_blocks3d_sd3.py:847-856."""
-    x, xp = sd3_resnet(wc, x, xp, pre + ".resnets.0", causal, tape=tape)  # (its records also give the attention's per-frame statistics)
-    if attention:
-        a = pre + ".attentions.0"
-        x, xp = spatial_attention(wc, x, a + ".group_norm", a + ".to_q", a + ".to_k", a + ".to_v", a + ".to_out.0", 1e-6, True,
-                                  gn_out=G32, xp=xp, tape=tape)
-    return sd3_resnet(wc, x, xp, pre + ".resnets.1", causal, tape=tape)
-
-
-def sd3_encoder(wc: WeightCache, x: torch.Tensor, cfg: dict, tape: Optional[list] = None) -> torch.Tensor:
-    """Encoder3D.forward, vae_models3d_sd3.py:162-208.  x: NCDHW (any float dtype) -> moments NCDHW.
-    tape: a list that receives what the backward pass of the TRAINABLE encoder (grad3d.sd3_encoder_backward) reads again; the
-    launches are the inference pass's own (same bits)."""
-    dtype = wc.p("conv_in.weight").dtype
-    causal = cfg["causal"]
-    boc = cfg["block_out_channels"]
-    pad = PC if causal else P1
-    h, hp = encoder_conv_in(wc, x, cfg, dtype, pad, REP, REP)
-    if tape is not None:
-        tape.append(dict(op="conv_in", x=x, pad=pad, mode_t=REP, mode_hw=REP, ndhwc_in=bool(cfg.get("ndhwc_in"))))
-    for i in range(len(boc)):
-        for j in range(cfg["layers_per_block"]):
-            h, hp = sd3_resnet(wc, h, hp, f"down_blocks.{i}.resnets.{j}", causal, tape=tape)
-        if i != len(boc) - 1:  # Downsample3D vae_blocks3d_sd3.py:224-239; time stride on even blocks (:115)
-            st = (2, 2, 2) if i % 2 == 0 else (1, 2, 2)
-            if tape is not None:
-                tape.append(dict(op="down3d", pre=f"down_blocks.{i}.downsamplers.0.conv", x=h, stride=st, pad=pad, mode_t=REP, mode_hw=REP))
-            h, hp = conv3(wc, h, f"down_blocks.{i}.downsamplers.0.conv", stride=st,
-                             pad=pad, pad_mode_t=REP, pad_mode_hw=REP, gn_out=G32)
-    h, hp = sd3_mid(wc, h, hp, "mid_block", causal, cfg["mid_block_add_attention"], tape=tape)
-    g = _norm(wc, h, hp, "conv_norm_out", 1e-6)
-    if tape is not None:
-        tape.append(dict(op="out3d", x=h, xp=hp, g=g, pad=pad, mode_t=REP, mode_hw=REP, eps=1e-6, norm="conv_norm_out"))
-    return conv3(wc, h, "conv_out", pad=pad, pad_mode_t=REP, pad_mode_hw=REP,
-                    prologue=L.PRO_GN_SILU, gn=g, out_mode=L.OUT_NCDHW)
-
-
-def sd3_decoder(wc: WeightCache, z: torch.Tensor, cfg: dict, tape: Optional[list] = None) -> torch.Tensor:
-    """Decoder3D.forward, vae_models3d_sd3.py:323-388.  z: NCDHW latents -> pixels NCDHW.
-    tape: receives what grad3d.sd3_decoder_backward reads again (training the decoder; the launches are the inference pass's)."""
-    dtype = wc.p("conv_in.weight").dtype
-    causal = cfg["causal"]
-    boc = cfg["block_out_channels"]
-    pad = PC if causal else P1
-    zin = z.shape[1]
-    cpad = ops.round_up(zin, 32 if (z.shape[2] == 1 and fold_t1()) else 16)
-    h = ops.ncdhw_to_ndhwc(z, cpad, dtype)
-    if tape is not None:
-        tape.append(dict(op="dec_in", x=h, pad=pad, mode_t=REP, mode_hw=REP, zin=zin))
-    h, hp = conv3(wc, h, "conv_in", cin_pad=cpad, pad=pad, pad_mode_t=REP, pad_mode_hw=REP,
-                     gn_out=G32)
-    h, hp = sd3_mid(wc, h, hp, "mid_block", causal, cfg["mid_block_add_attention"], tape=tape)
-    for i in range(len(boc)):
-        for j in range(cfg["layers_per_block"] + 1):
-            h, hp = sd3_resnet(wc, h, hp, f"up_blocks.{i}.resnets.{j}", causal, tape=tape)
-        if i != len(boc) - 1:  # Upsample3D vae_blocks3d_sd3.py:314-364; up_time on even blocks (vae_models3d_sd3.py:289)
-            up_time = i % 2 == 0
-            if tape is not None:
-                tape.append(dict(op="up3d", pre=f"up_blocks.{i}.upsamplers.0.conv", x=h, pad=pad, mode_t=REP, mode_hw=REP, up_time=up_time))
-            h, hp = upsample_conv(wc, h, f"up_blocks.{i}.upsamplers.0.conv", pad, REP, REP, up_time)
-    g = _norm(wc, h, hp, "conv_norm_out", 1e-6)
-    if tape is not None:
-        tape.append(dict(op="out3d", x=h, xp=hp, g=g, pad=pad, mode_t=REP, mode_hw=REP, eps=1e-6, norm="conv_norm_out"))
-    return decoder_conv_out(wc, h, g, pad, REP, REP, u8=bool(cfg.get("u8_out")))
-
-
-# --------------------------------------------------------------------------------------------------------
-# SURVEY 8(f) rank 4: the frozen 2-D "constraint" decoder of the training path (SD3 image VAE decoder per frame)
-# --------------------------------------------------------------------------------------------------------
-def c2d_resnet(wc: WeightCache, x: torch.Tensor, xp, pre: str, want_stats: bool = True, tape: Optional[list] = None,
-               sc: str = ".conv_shortcut"):
-    """ResnetBlock2D.forward, lvdm/modules/diffusionmodules/vae_blocks_sd3.py:368-421, on [frames,1,H,W,C]: GN(eps 1e-6)+SiLU
-    fused into conv1 and conv2 (per-frame 3x3, zero pad), 1x1 shortcut and residual add in conv2's launch."""
-    g1 = _norm(wc, x, xp, pre + ".norm1", 1e-6)
-    # (this launch always keeps its prologue fused: no prepass decision in front of it)
-    h, hp = ops.conv(x, wc.conv(pre + ".conv1", (1, 3, 3), act_norm=pre + ".norm1"), pad=P2D,
-                     pad_mode_hw=ZERO, prologue=L.PRO_GN_SILU, gn=g1, gn_out=G32)
-    g2 = ops.gn_finalize(hp, *wc.norm(pre + ".norm2"), 1e-6)
-    if tape is not None:
+    g1 = _norm(wc, x, xp, pre + ".norm1", eps)
+    if conv1 is None:  # (this launch always keeps its prologue fused: no prepass decision in front of it)
+        h, hp = ops.conv(x, wc.conv(pre + ".conv1", (1, 3, 3), act_norm=pre + ".norm1"), pad=P2D, pad_mode_hw=ZERO,
+                         prologue=L.PRO_GN_SILU, gn=g1, gn_out=G32)
+    else:
+        pad, mt, mhw = conv1
+        h, hp = conv3(wc, x, pre + ".conv1", pad=pad, pad_mode_t=mt, pad_mode_hw=mhw, prologue=L.PRO_GN_SILU, gn=g1, gn_out=G32,
+                      act_norm=pre + ".norm1")
+    g2 = ops.gn_finalize(hp, *wc.norm(pre + ".norm2"), eps)
+    if tape is not None and conv1 is None:      # what the frozen 2-D decoder's input-gradient pass (grad.py) reads again
         tape.append(dict(op="resnet", pre=pre, x=x, xp=xp, h=h, hp=hp))
+    elif tape is not None:                      # ... and the training-side backward (grad3d.py): with the statistics and the padding
+        tape.append(dict(op="resnet3d", pre=pre, x=x, xp=xp, h=h, hp=hp, g1=g1, g2=g2, pad=pad, mode_t=mt, mode_hw=mhw, eps=eps, sc=sc))
     return resnet_tail(wc, x, h, pre, pre + sc, g2, want_stats)
 
 
-def constraint_decoder2d(wc: WeightCache, z: torch.Tensor, cfg: dict, tape: Optional[list] = None) -> torch.Tensor:
-    """DecoderWith3DWrapper.forward over Decoder.forward (lvdm/modules/diffusionmodules/vae_models_sd3.py:297-362, 390-398):
-    z NCDHW [b,c,t,h,w] -> pixels [b,3,t,8h,8w], every frame decoded on its own ("b c t h w -> (b t) c h w": frames are the
-    batch rows here, so every GroupNorm is per frame as in the reference).  tape: a list that receives what the input-gradient
-    pass of the frozen decoder (grad.constraint_decoder2d_backward) reads again."""
-    dtype = wc.p("conv_in.weight").dtype
-    boc = cfg["block_out_channels"]
-    B, zin, T = z.shape[0], z.shape[1], z.shape[2]
-    cpad = ops.round_up(zin, 32)
-    h = ops.ncdhw_to_ndhwc(z, cpad, dtype)
-    h = h.view(B * T, 1, h.shape[2], h.shape[3], cpad)
-    h, hp = ops.conv(h, wc.conv("conv_in", (1, 3, 3), cin_pad=cpad), pad=P2D, pad_mode_hw=ZERO, gn_out=G32)
-    attn = cfg["mid_block_add_attention"]
-    h, hp = c2d_resnet(wc, h, hp, "mid_block.resnets.0", want_stats=not attn, tape=tape)  # UNetMidBlock2D.forward, vae_blocks_sd3.py:669-681
-    if attn:
-        a = "mid_block.attentions.0"
-        h, hp = spatial_attention(wc, h, a + ".group_norm", a + ".to_q", a + ".to_k", a + ".to_v", a + ".to_out.0", 1e-6, True,
-                                  gn_out=G32, tape=tape)
-    h, hp = c2d_resnet(wc, h, hp, "mid_block.resnets.1", tape=tape)
-    for i in range(len(boc)):  # UpDecoderBlock2D.forward, vae_blocks_sd3.py:536-547
-        for j in range(cfg["layers_per_block"] + 1):
-            h, hp = c2d_resnet(wc, h, hp, f"up_blocks.{i}.resnets.{j}", tape=tape)
-        if i != len(boc) - 1:  # Upsample2D.forward :178-230: nearest x2 + conv 3x3 (zero pad), as four folded 1x2x2 phase convs
-            if tape is not None:
-                tape.append(dict(op="up", pre=f"up_blocks.{i}.upsamplers.0.conv"))
-            h, hp = ops.conv(h, wc.conv_upfold2d(f"up_blocks.{i}.upsamplers.0.conv"), pad=P2D, pad_mode_hw=ZERO, upsample2x=2,
-                             gn_out=G32)
-    g = _norm(wc, h, hp, "conv_norm_out", 1e-6)
-    if tape is not None:
-        tape.append(dict(op="out", x=h, xp=hp, B=B, T=T, zin=zin))
-    y = ops.conv(h, wc.conv("conv_out", (1, 3, 3)), pad=P2D, pad_mode_hw=ZERO, prologue=L.PRO_GN_SILU, gn=g,
-                 out_mode=L.OUT_NCDHW)                      # [b*t, 3, 1, H, W]
-    return y.view(B, T, y.shape[1], y.shape[3], y.shape[4]).transpose(1, 2).contiguous()
+c2d_resnet = functools.partial(resnet, eps=1e-6, conv1=None, sc=".conv_shortcut")  # ResnetBlock2D of the SD3 image decoder
+
+
+def _mid(wc: WeightCache, x: torch.Tensor, xp, sp: Spelling, block, eps: float, attention, tape: Optional[list],
+         attn_from_records: bool = True):
+    """the mid block (UNetMidBlock3D / 2D, vae_blocks3d_sd3.py:847-856, vae_blocks_sd3.py:669-681; mid.block_1 / attn_1 / block_2 of
+    vae_models.py and model.py).  block(x, xp, pre, want_stats): the family's ResnetBlock; attention: False, True (spatial, with
+    residual) or "spatial_temporal".  attn_from_records: the attention's per-frame statistics come from the first block's records;
+    False (the SD3 image decoder): a statistics pass over the tensor, and the first block emits records only when no attention follows."""
+    x, xp = block(x, xp, sp.mid[0], attn_from_records or not attention)
+    if attention == "spatial_temporal":
+        x, xp = v3_attn_spatial_temporal(wc, x, sp.attn, xp=xp, tape=tape)
+    elif attention:
+        x, xp = spatial_attention(wc, x, *sp.attn_names, eps, True, gn_out=G32, xp=xp if attn_from_records else None, tape=tape)
+    return block(x, xp, sp.mid[1], True)
 
 
 # --------------------------------------------------------------------------------------------------------
-# SURVEY 8(f) rank 4, second half: the frozen 2-D encoder / decoder of the SD2.1-compatible family (LDM layout) per frame
+# SURVEY 8(f) rank 4: the frozen 2-D image VAEs of the training path, per frame -- the SD3 image decoder ("constraint" decoder of the
+# vae3d_sd3 family, diffusers spelling) and the SD2.1 image VAE's halves (LDM spelling)
 # --------------------------------------------------------------------------------------------------------
 def _frames_in(x: torch.Tensor, cpad: int, dtype: torch.dtype) -> torch.Tensor:
     """[b,c,t,h,w] -> NDHWC [(b t),1,h,w,cpad]: 'b c t h w -> (b t) c h w' (frames are the batch rows: every GroupNorm is per frame)"""
@@ -812,27 +765,80 @@ def _frames_out(y: torch.Tensor, B: int, T: int) -> torch.Tensor:
     return y.view(B, T, y.shape[1], y.shape[3], y.shape[4]).transpose(1, 2).contiguous()
 
 
+def _decoder2d(wc: WeightCache, z: torch.Tensor, cfg: dict, tape: Optional[list], sp: Spelling, *, attention: bool,
+               attn_from_records: bool, ldm_latent: bool) -> torch.Tensor:
+    """conv_in -> mid -> levels of ResnetBlocks with Upsample (nearest x2 + 3x3, as four folded 1x2x2 phase convs) from the coarsest
+    -> norm_out + SiLU + conv_out, every frame on its own.  z NCDHW [b,c,t,h,w] -> pixels [b,out,t,f*h,f*w].
+    tape: a list that receives what the input-gradient pass of the frozen decoder (grad.decoder2d_backward) reads again; None
+    (inference): the launches are exactly those of the untaped pass.  What the two families do differently in their launches:
+      attention          a mid block without attention exists in the diffusers configuration only
+      attn_from_records  see _mid
+      ldm_latent         the latents are channel-padded to 32 -- to 128 in front of `post_quant_conv` (the 1x1 of the legacy
+                         checkpoints), whose output is padded to 32; otherwise to round_up(channels, 32)"""
+    dtype = wc.p("conv_in.weight").dtype
+    B, zin, T = z.shape[0], z.shape[1], z.shape[2]
+    n, nb = len(cfg[sp.levels]), cfg[sp.blocks]
+    pqc = ldm_latent and wc.has("post_quant_conv.weight")
+    if pqc:
+        h = _frames_in(z, 128, dtype)
+        pq = wc.conv("post_quant_conv", (1, 1, 1), cin_pad=128)
+        h = ops.conv(_flat(h), pq, cout_pad=32).view(*h.shape[:-1], 32)
+    else:
+        h = _frames_in(z, 32 if ldm_latent else ops.round_up(zin, 32), dtype)
+    cpad = h.shape[-1]
+
+    def block(h, hp, pre, want_stats=True):
+        return resnet(wc, h, hp, pre, want_stats, tape, eps=1e-6, conv1=None, sc=sp.shortcut)
+    h, hp = ops.conv(h, wc.conv("conv_in", (1, 3, 3), cin_pad=cpad), pad=P2D, pad_mode_hw=ZERO, gn_out=G32)
+    h, hp = _mid(wc, h, hp, sp, block, 1e-6, attention, tape, attn_from_records)
+    for k, i in enumerate(sp.up_levels(n)):
+        for j in range(nb + 1):
+            h, hp = block(h, hp, sp.up_block.format(i=i, j=j))
+        if k != n - 1:
+            pre = sp.up_conv.format(i=i)
+            if tape is not None:
+                tape.append(dict(op="up", pre=pre))
+            h, hp = ops.conv(h, wc.conv_upfold2d(pre), pad=P2D, pad_mode_hw=ZERO, upsample2x=2, gn_out=G32)
+    g = _norm(wc, h, hp, sp.norm_out, 1e-6)
+    if tape is not None:
+        tape.append(dict(op="out", x=h, xp=hp, B=B, T=T, zin=zin, names=sp, **({"post_quant_conv": pqc} if ldm_latent else {})))
+    y = ops.conv(h, wc.conv("conv_out", (1, 3, 3)), pad=P2D, pad_mode_hw=ZERO, prologue=L.PRO_GN_SILU, gn=g, out_mode=L.OUT_NCDHW)
+    return _frames_out(y, B, T)
+
+
+def constraint_decoder2d(wc: WeightCache, z: torch.Tensor, cfg: dict, tape: Optional[list] = None) -> torch.Tensor:
+    """DecoderWith3DWrapper.forward over Decoder.forward (lvdm/modules/diffusionmodules/vae_models_sd3.py:297-362, 390-398; blocks
+    vae_blocks_sd3.py:178-230, 536-547): the SD3 image decoder, z [b,c,t,h,w] -> pixels [b,3,t,8h,8w]."""
+    return _decoder2d(wc, z, cfg, tape, DIFFUSERS, attention=cfg["mid_block_add_attention"], attn_from_records=False, ldm_latent=False)
+
+
+def ldm2d_decoder(wc: WeightCache, z: torch.Tensor, cfg: dict, tape: Optional[list] = None) -> torch.Tensor:
+    """DecoderWith3DWrapper.forward over Decoder.forward (lvdm/modules/diffusionmodules/model.py:728-772, 820-830): the SD2.1 image
+    decoder behind `post_quant_conv`, z [b,zc,t,h,w] -> pixels [b,out_ch,t,f*h,f*w]."""
+    return _decoder2d(wc, z, cfg, tape, LDM, attention=True, attn_from_records=True, ldm_latent=True)
+
+
 def ldm2d_encoder(wc: WeightCache, x: torch.Tensor, cfg: dict) -> torch.Tensor:
     """EncoderWith3DWrapper.forward over Encoder.forward (lvdm/modules/diffusionmodules/model.py:587-614, 877-887): every frame
-    through conv_in -> levels of ResnetBlocks (GroupNorm eps 1e-6 + swish + 3x3, 1x1 nin_shortcut) with Downsample (zero pad
-    right / bottom, 3x3 stride 2) -> mid (block_1, single-head attn_1, block_2) -> norm_out + swish + conv_out -> quant_conv 1x1.
-    x NCDHW [b,c,t,h,w] -> moments [b,2z,t,h/f,w/f]."""
+    through conv_in -> levels of ResnetBlocks with Downsample (zero pad right / bottom, 3x3 stride 2) -> mid -> norm_out + swish +
+    conv_out -> quant_conv 1x1.  x NCDHW [b,c,t,h,w] -> moments [b,2z,t,h/f,w/f]."""
+    sp = LDM
     dtype = wc.p("conv_in.weight").dtype
     B, T = x.shape[0], x.shape[2]
-    nlev = len(cfg["ch_mult"])
+    n, nb = len(cfg[sp.levels]), cfg[sp.blocks]
+
+    def block(h, hp, pre, want_stats=True):
+        return resnet(wc, h, hp, pre, want_stats, eps=1e-6, conv1=None, sc=sp.shortcut)
     h = _frames_in(x, 32, dtype)
     h, hp = ops.conv(h, wc.conv("conv_in", (1, 3, 3), cin_pad=32), pad=P2D, pad_mode_hw=ZERO, gn_out=G32)
-    for lvl in range(nlev):
-        for j in range(cfg["num_res_blocks"]):
-            h, hp = c2d_resnet(wc, h, hp, f"down.{lvl}.block.{j}", sc=".nin_shortcut")
-        if lvl != nlev - 1:  # Downsample: F.pad (0,1,0,1) zeros, conv 3x3 stride 2 pad 0 (model.py:88-95)
-            h, hp = ops.conv(h, wc.conv(f"down.{lvl}.downsample.conv", (1, 3, 3)), stride=(1, 2, 2), pad=((0, 0), (0, 1), (0, 1)),
+    for i in range(n):
+        for j in range(nb):
+            h, hp = block(h, hp, sp.down_block.format(i=i, j=j))
+        if i != n - 1:  # Downsample: F.pad (0,1,0,1) zeros, conv 3x3 stride 2 pad 0 (model.py:88-95)
+            h, hp = ops.conv(h, wc.conv(sp.down_conv.format(i=i), (1, 3, 3)), stride=(1, 2, 2), pad=((0, 0), (0, 1), (0, 1)),
                              pad_mode_hw=ZERO, gn_out=G32)
-    h, hp = c2d_resnet(wc, h, hp, "mid.block_1", sc=".nin_shortcut")
-    a = "mid.attn_1"
-    h, hp = spatial_attention(wc, h, a + ".norm", a + ".q", a + ".k", a + ".v", a + ".proj_out", 1e-6, True, gn_out=G32, xp=hp)
-    h, hp = c2d_resnet(wc, h, hp, "mid.block_2", sc=".nin_shortcut")
-    g = _norm(wc, h, hp, "norm_out", 1e-6)
+    h, hp = _mid(wc, h, hp, sp, block, 1e-6, True, None)
+    g = _norm(wc, h, hp, sp.norm_out, 1e-6)
     zc = wc.p("conv_out.weight").shape[0]
     m = ops.conv(h, wc.conv("conv_out", (1, 3, 3)), pad=P2D, pad_mode_hw=ZERO, prologue=L.PRO_GN_SILU, gn=g,
                  cout_pad=ops.round_up(zc, 128) if wc.has("quant_conv.weight") else None,
@@ -844,92 +850,31 @@ def ldm2d_encoder(wc: WeightCache, x: torch.Tensor, cfg: dict) -> torch.Tensor:
     return _frames_out(m, B, T)
 
 
-def ldm2d_decoder(wc: WeightCache, z: torch.Tensor, cfg: dict, tape: Optional[list] = None) -> torch.Tensor:
-    """DecoderWith3DWrapper.forward over Decoder.forward (model.py:728-772, 820-830): post_quant_conv 1x1 -> conv_in -> mid ->
-    levels (num_res_blocks + 1 ResnetBlocks, Upsample = nearest x2 + 3x3) from the coarsest -> norm_out + swish + conv_out.
-    z NCDHW [b,zc,t,h,w] -> pixels [b,out_ch,t,f*h,f*w].  tape: a list that receives what the input-gradient pass of the frozen
-    decoder (grad.ldm2d_decoder_backward) reads again; None (inference): the launches are exactly those of the untaped pass."""
-    dtype = wc.p("conv_in.weight").dtype
-    B, zin, T = z.shape[0], z.shape[1], z.shape[2]
-    nlev = len(cfg["ch_mult"])
-    pqc = wc.has("post_quant_conv.weight")
-    if pqc:
-        h = _frames_in(z, 128, dtype)
-        pq = wc.conv("post_quant_conv", (1, 1, 1), cin_pad=128)
-        h = ops.conv(_flat(h), pq, cout_pad=32).view(*h.shape[:-1], 32)
-    else:
-        h = _frames_in(z, 32, dtype)
-    h, hp = ops.conv(h, wc.conv("conv_in", (1, 3, 3), cin_pad=32), pad=P2D, pad_mode_hw=ZERO, gn_out=G32)
-    h, hp = c2d_resnet(wc, h, hp, "mid.block_1", sc=".nin_shortcut", tape=tape)
-    a = "mid.attn_1"
-    h, hp = spatial_attention(wc, h, a + ".norm", a + ".q", a + ".k", a + ".v", a + ".proj_out", 1e-6, True, gn_out=G32, xp=hp,
-                              tape=tape)
-    h, hp = c2d_resnet(wc, h, hp, "mid.block_2", sc=".nin_shortcut", tape=tape)
-    for lvl in reversed(range(nlev)):
-        for j in range(cfg["num_res_blocks"] + 1):
-            h, hp = c2d_resnet(wc, h, hp, f"up.{lvl}.block.{j}", sc=".nin_shortcut", tape=tape)
-        if lvl != 0:  # Upsample: nearest x2 + conv 3x3 pad 1 (model.py:68-75), as four folded 1x2x2 phase convs
-            if tape is not None:
-                tape.append(dict(op="up", pre=f"up.{lvl}.upsample.conv"))
-            h, hp = ops.conv(h, wc.conv_upfold2d(f"up.{lvl}.upsample.conv"), pad=P2D, pad_mode_hw=ZERO, upsample2x=2, gn_out=G32)
-    g = _norm(wc, h, hp, "norm_out", 1e-6)
-    if tape is not None:
-        tape.append(dict(op="out", x=h, xp=hp, B=B, T=T, zin=zin, post_quant_conv=pqc))
-    y = ops.conv(h, wc.conv("conv_out", (1, 3, 3)), pad=P2D, pad_mode_hw=ZERO, prologue=L.PRO_GN_SILU, gn=g, out_mode=L.OUT_NCDHW)
-    return _frames_out(y, B, T)
+# --------------------------------------------------------------------------------------------------------
+# the 3-D networks of both families
+# --------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class Geometry:
+    """what the 3-D convs of a family do at their borders; every conv is a (pad, time mode, H / W mode) triple"""
+    eps: float                      # of every GroupNorm
+    conv: Callable                  # causal -> the triple of the stride-1 3x3x3 convs (conv_in, conv1 of the blocks, conv_out)
+    down: Optional[tuple]           # Downsample3D's triple; None: the family's own
+    up: Optional[tuple]             # Upsample3D's; None: the family's own
+    # does an up block double the time axis?  k: its position counted from the coarsest block, i: the index in its name.  The two
+    # families' parities do NOT agree for an odd number of levels (k = n - 1 - i): each keeps its own
+    up_time: Callable
 
 
-# --------------------------------------------------------------------------------------------------------
-# vae3d family
-# --------------------------------------------------------------------------------------------------------
 def _v3_pad(causal: bool):
     # CausalConv3d (vae_models.py:298-328): zero pad W,H; replicate T front 2.  nn.Conv3d(padding=1): zero everywhere.
     return (PC, REP, ZERO) if causal else (P1, ZERO, ZERO)
 
 
-def v3_resnet(wc: WeightCache, x: torch.Tensor, xp, pre: str, causal: bool, want_stats: bool = True, tape: Optional[list] = None):
-    """ResnetBlock3D.forward, vae_models.py:390-410 (GN eps 1e-5, swish, nin_shortcut 1x1x1).
-    xp: GroupNorm partials of x from its producer (or None).  Returns (out, partials of out or None)."""
-    pad, mt, mhw = _v3_pad(causal)
-    g1 = _norm(wc, x, xp, pre + ".norm1", 1e-5)
-    h, hp = conv3(wc, x, pre + ".conv1", pad=pad, pad_mode_t=mt, pad_mode_hw=mhw, prologue=L.PRO_GN_SILU,
-                     gn=g1, gn_out=G32, act_norm=pre + ".norm1")
-    g2 = ops.gn_finalize(hp, *wc.norm(pre + ".norm2"), 1e-5)
-    if tape is not None:
-        tape.append(dict(op="resnet3d", pre=pre, x=x, xp=xp, h=h, hp=hp, g1=g1, g2=g2, pad=pad, mode_t=mt, mode_hw=mhw, eps=1e-5,
-                         sc=".nin_shortcut"))
-    return resnet_tail(wc, x, h, pre, pre + ".nin_shortcut", g2, want_stats)
-
-
-def v3_encoder(wc: WeightCache, x: torch.Tensor, cfg: dict, tape: Optional[list] = None) -> torch.Tensor:
-    """Encoder.forward, vae_models.py:790-823.  tape: see sd3_encoder (grad3d.py trains this network too)."""
-    dtype = wc.p("conv_in.weight").dtype
-    causal = cfg["causal"]
-    pad, mt, mhw = _v3_pad(causal)
-    nlev = len(cfg["ch_mult"])
-    h, hp = encoder_conv_in(wc, x, cfg, dtype, pad, mt, mhw)
-    if tape is not None:
-        tape.append(dict(op="conv_in", x=x, pad=pad, mode_t=mt, mode_hw=mhw, ndhwc_in=bool(cfg.get("ndhwc_in"))))
-    for lvl in range(nlev):
-        for j in range(cfg["num_res_blocks"]):
-            h, hp = v3_resnet(wc, h, hp, f"down.{lvl}.block.{j}", causal, tape=tape)
-        if lvl != nlev - 1:  # Downsample3D vae_models.py:251-263: zero pad right/bottom, replicate T front 2
-            st = (2, 2, 2) if lvl % 2 == 0 else (1, 2, 2)
-            dpad = ((2, 0), (0, 1), (0, 1))
-            if tape is not None:
-                tape.append(dict(op="down3d", pre=f"down.{lvl}.downsample.conv", x=h, stride=st, pad=dpad, mode_t=REP, mode_hw=ZERO))
-            h, hp = conv3(wc, h, f"down.{lvl}.downsample.conv", stride=st, pad=dpad,
-                             pad_mode_t=REP, pad_mode_hw=ZERO, gn_out=G32)
-    h, hp = v3_resnet(wc, h, hp, "mid.block_1", causal, tape=tape)
-    a = "mid.attn_1"
-    h, hp = spatial_attention(wc, h, a + ".norm", a + ".q", a + ".k", a + ".v", a + ".proj_out", 1e-5, True, gn_out=G32, xp=hp,
-                              tape=tape)
-    h, hp = v3_resnet(wc, h, hp, "mid.block_2", causal, tape=tape)
-    g = _norm(wc, h, hp, "norm_out", 1e-5)
-    if tape is not None:
-        tape.append(dict(op="out3d", x=h, xp=hp, g=g, pad=pad, mode_t=mt, mode_hw=mhw, eps=1e-5, norm="norm_out"))
-    return conv3(wc, h, "conv_out", pad=pad, pad_mode_t=mt, pad_mode_hw=mhw, prologue=L.PRO_GN_SILU, gn=g,
-                    out_mode=L.OUT_NCDHW)
+# vae3d_sd3 (vae_blocks3d_sd3.py): replicate everywhere, causal T(2,0) or (1,1); up_time on even blocks (vae_models3d_sd3.py:289)
+SD3_GEO = Geometry(1e-6, lambda causal: (PC if causal else P1, REP, REP), None, None, lambda k, i: k % 2 == 0)
+# vae3d (vae_models.py): Downsample3D :251-263 pads zeros right / bottom and replicates T front 2; Upsample3D :214-235 is built
+# non-causal whatever the decoder is (:936): zero pad W,H, replicate T (1,1); up_time on odd levels
+V3_GEO = Geometry(1e-5, _v3_pad, (((2, 0), (0, 1), (0, 1)), REP, ZERO), (P1, REP, ZERO), lambda k, i: i % 2 == 1)
 
 
 def v3_attn_spatial_temporal(wc: WeightCache, x: torch.Tensor, a: str, xp=None, tape: Optional[list] = None):
@@ -947,31 +892,81 @@ def v3_attn_spatial_temporal(wc: WeightCache, x: torch.Tensor, a: str, xp=None, 
     return conv1x1(wc, o, a + ".proj_out_t", residual=x, gn_out=G32)
 
 
-def v3_decoder(wc: WeightCache, z: torch.Tensor, cfg: dict, tape: Optional[list] = None) -> torch.Tensor:
-    """Decoder.forward, vae_models.py:960-1002.  tape: see sd3_decoder."""
+def _encoder3d(wc: WeightCache, x: torch.Tensor, cfg: dict, tape: Optional[list], sp: Spelling, geo: Geometry, attention) -> torch.Tensor:
+    """x: NCDHW (any float dtype) -> moments NCDHW.  tape: a list that receives what the backward pass of the TRAINABLE encoder
+    (grad3d.sd3_net_backward) reads again; the launches are the inference pass's own (same bits)."""
     dtype = wc.p("conv_in.weight").dtype
-    causal = cfg["causal"]
-    pad, mt, mhw = _v3_pad(causal)
-    nlev = len(cfg["ch_mult"])
+    conv = pad, mt, mhw = geo.conv(cfg["causal"])
+    dpad, dmt, dmhw = geo.down or conv
+    n, nb = len(cfg[sp.levels]), cfg[sp.blocks]
+
+    def block(h, hp, pre, want_stats=True):
+        return resnet(wc, h, hp, pre, want_stats, tape, eps=geo.eps, conv1=conv, sc=sp.shortcut)
+    h, hp = encoder_conv_in(wc, x, cfg, dtype, pad, mt, mhw)
+    if tape is not None:
+        tape.append(dict(op="conv_in", x=x, pad=pad, mode_t=mt, mode_hw=mhw, ndhwc_in=bool(cfg.get("ndhwc_in"))))
+    for i in range(n):
+        for j in range(nb):
+            h, hp = block(h, hp, sp.down_block.format(i=i, j=j))
+        if i != n - 1:  # Downsample3D; time stride on even levels (vae_blocks3d_sd3.py:115, 224-239)
+            st = (2, 2, 2) if i % 2 == 0 else (1, 2, 2)
+            pre = sp.down_conv.format(i=i)
+            if tape is not None:
+                tape.append(dict(op="down3d", pre=pre, x=h, stride=st, pad=dpad, mode_t=dmt, mode_hw=dmhw))
+            h, hp = conv3(wc, h, pre, stride=st, pad=dpad, pad_mode_t=dmt, pad_mode_hw=dmhw, gn_out=G32)
+    h, hp = _mid(wc, h, hp, sp, block, geo.eps, attention, tape)
+    g = _norm(wc, h, hp, sp.norm_out, geo.eps)
+    if tape is not None:
+        tape.append(dict(op="out3d", x=h, xp=hp, g=g, pad=pad, mode_t=mt, mode_hw=mhw, eps=geo.eps, norm=sp.norm_out))
+    return conv3(wc, h, "conv_out", pad=pad, pad_mode_t=mt, pad_mode_hw=mhw, prologue=L.PRO_GN_SILU, gn=g, out_mode=L.OUT_NCDHW)
+
+
+def _decoder3d(wc: WeightCache, z: torch.Tensor, cfg: dict, tape: Optional[list], sp: Spelling, geo: Geometry, attention) -> torch.Tensor:
+    """z: NCDHW latents -> pixels NCDHW.  tape: receives what grad3d.sd3_net_backward reads again (training the decoder; the
+    launches are the inference pass's)."""
+    dtype = wc.p("conv_in.weight").dtype
+    conv = pad, mt, mhw = geo.conv(cfg["causal"])
+    upad, umt, umhw = geo.up or conv
+    n, nb = len(cfg[sp.levels]), cfg[sp.blocks]
+
+    def block(h, hp, pre, want_stats=True):
+        return resnet(wc, h, hp, pre, want_stats, tape, eps=geo.eps, conv1=conv, sc=sp.shortcut)
     zin = z.shape[1]
     cpad = ops.round_up(zin, 32 if (z.shape[2] == 1 and fold_t1()) else 16)
     h = ops.ncdhw_to_ndhwc(z, cpad, dtype)
     if tape is not None:
         tape.append(dict(op="dec_in", x=h, pad=pad, mode_t=mt, mode_hw=mhw, zin=zin))
-    h, hp = conv3(wc, h, "conv_in", cin_pad=cpad, pad=pad, pad_mode_t=mt, pad_mode_hw=mhw,
-                     gn_out=G32)
-    h, hp = v3_resnet(wc, h, hp, "mid.block_1", causal, tape=tape)
-    h, hp = v3_attn_spatial_temporal(wc, h, "mid.attn_1", xp=hp, tape=tape)
-    h, hp = v3_resnet(wc, h, hp, "mid.block_2", causal, tape=tape)
-    for lvl in reversed(range(nlev)):
-        for j in range(cfg["num_res_blocks"] + 1):
-            h, hp = v3_resnet(wc, h, hp, f"up.{lvl}.block.{j}", causal, tape=tape)
-        if lvl != 0:  # Upsample3D vae_models.py:214-235 (built non-causal, :936): zero pad W,H, replicate T (1,1)
-            up_time = lvl % 2 == 1
+    h, hp = conv3(wc, h, "conv_in", cin_pad=cpad, pad=pad, pad_mode_t=mt, pad_mode_hw=mhw, gn_out=G32)
+    h, hp = _mid(wc, h, hp, sp, block, geo.eps, attention, tape)
+    for k, i in enumerate(sp.up_levels(n)):
+        for j in range(nb + 1):
+            h, hp = block(h, hp, sp.up_block.format(i=i, j=j))
+        if k != n - 1:  # Upsample3D (vae_blocks3d_sd3.py:314-364, vae_models.py:214-235)
+            up_time, pre = geo.up_time(k, i), sp.up_conv.format(i=i)
             if tape is not None:
-                tape.append(dict(op="up3d", pre=f"up.{lvl}.upsample.conv", x=h, pad=P1, mode_t=REP, mode_hw=ZERO, up_time=up_time))
-            h, hp = upsample_conv(wc, h, f"up.{lvl}.upsample.conv", P1, REP, ZERO, up_time)
-    g = _norm(wc, h, hp, "norm_out", 1e-5)
+                tape.append(dict(op="up3d", pre=pre, x=h, pad=upad, mode_t=umt, mode_hw=umhw, up_time=up_time))
+            h, hp = upsample_conv(wc, h, pre, upad, umt, umhw, up_time)
+    g = _norm(wc, h, hp, sp.norm_out, geo.eps)
     if tape is not None:
-        tape.append(dict(op="out3d", x=h, xp=hp, g=g, pad=pad, mode_t=mt, mode_hw=mhw, eps=1e-5, norm="norm_out"))
+        tape.append(dict(op="out3d", x=h, xp=hp, g=g, pad=pad, mode_t=mt, mode_hw=mhw, eps=geo.eps, norm=sp.norm_out))
     return decoder_conv_out(wc, h, g, pad, mt, mhw, u8=bool(cfg.get("u8_out")))
+
+
+def sd3_encoder(wc: WeightCache, x: torch.Tensor, cfg: dict, tape: Optional[list] = None) -> torch.Tensor:
+    """Encoder3D.forward, vae_models3d_sd3.py:162-208"""
+    return _encoder3d(wc, x, cfg, tape, DIFFUSERS, SD3_GEO, cfg["mid_block_add_attention"])
+
+
+def sd3_decoder(wc: WeightCache, z: torch.Tensor, cfg: dict, tape: Optional[list] = None) -> torch.Tensor:
+    """Decoder3D.forward, vae_models3d_sd3.py:323-388"""
+    return _decoder3d(wc, z, cfg, tape, DIFFUSERS, SD3_GEO, cfg["mid_block_add_attention"])
+
+
+def v3_encoder(wc: WeightCache, x: torch.Tensor, cfg: dict, tape: Optional[list] = None) -> torch.Tensor:
+    """Encoder.forward, vae_models.py:790-823 (spatial attention in the mid block, always)"""
+    return _encoder3d(wc, x, cfg, tape, LDM, V3_GEO, True)
+
+
+def v3_decoder(wc: WeightCache, z: torch.Tensor, cfg: dict, tape: Optional[list] = None) -> torch.Tensor:
+    """Decoder.forward, vae_models.py:960-1002 (MemoryEfficientAttnVideoBlock in the mid block)"""
+    return _decoder3d(wc, z, cfg, tape, LDM, V3_GEO, "spatial_temporal")

@@ -1,10 +1,11 @@
-"""Input gradients through the FROZEN 2-D constraint decoder on the MI355X kernels (training-side codec use).
+"""Input gradients through the FROZEN 2-D constraint decoders on the MI355X kernels (training-side codec use).
 
 The reference trains the 3-D VAE with a latent-compatibility loss: the latents go through the frozen SD3 image decoder
 (`self.constraint_decoder.requires_grad_(False)`, `xrec_2d = self.constraint_decoder(z)`, lvdm/models/autoencoder.py:1057-1069) and
 the loss back-propagates THROUGH that decoder into z (and on into the encoder).  What the frozen module contributes to the
-backward pass is autograd's input gradient of each of its ops -- no weight gradients.  This file is that pass for
-`engine.constraint_decoder2d`:
+backward pass is autograd's input gradient of each of its ops -- no weight gradients.  This file is that pass for the per-frame 2-D
+decoder program of cvvae_amd/engine.py in both spellings -- `engine.constraint_decoder2d` (SD3 image decoder) and
+`engine.ldm2d_decoder` (SD2.1 image decoder, with `post_quant_conv`): one walker (`decoder2d_backward`), one autograd node:
 
   conv / linear   grad_input = conv(gy, W with taps flipped and Cin/Cout exchanged), same zero padding  -> the forward MFMA kernel
                   (backward.conv_dgrad / dgrad1x1; nn.Conv2d(3x3, padding=1) and nn.Linear of vae_blocks_sd3.py / diffusers Attention)
@@ -28,10 +29,11 @@ from .engine import P2D, WeightCache
 K2D = (1, 3, 3)
 
 
-def resnet_backward(wc: WeightCache, g: torch.Tensor, e: dict) -> torch.Tensor:
-    """ResnetBlock2D (vae_blocks_sd3.py:368-421): y = conv2(silu(norm2(h))) + shortcut(x), h = conv1(silu(norm1(x))).  g = dL/dy."""
+def resnet_backward(wc: WeightCache, g: torch.Tensor, e: dict, shortcut: str = "conv_shortcut") -> torch.Tensor:
+    """ResnetBlock2D (vae_blocks_sd3.py:368-421; `nin_shortcut`: ResnetBlock of model.py:98-155): y = conv2(silu(norm2(h))) +
+    shortcut(x), h = conv1(silu(norm1(x))).  g = dL/dy."""
     pre = e["pre"] + "."
-    return backward.resnet_backward(wc, g, None, block_names(wc, pre, "conv_shortcut"), e["x"], e["xp"], e["h"], e["hp"], 1e-6,
+    return backward.resnet_backward(wc, g, None, block_names(wc, pre, shortcut), e["x"], e["xp"], e["h"], e["hp"], 1e-6,
                                     conv1=(K2D, {}), conv2=(K2D, P2D), dgrad1=lambda gh: conv_dgrad(wc, gh, pre + "conv1", K2D, P2D))
 
 
@@ -77,36 +79,56 @@ def attention_backward(wc: WeightCache, g: torch.Tensor, e: dict, grads: Optiona
                        per_frame=True)
 
 
-def constraint_decoder2d_backward(wc: WeightCache, tape: List[dict], gy: torch.Tensor) -> torch.Tensor:
-    """gy = dL/d(output) [b,3,t,H,W] of engine.constraint_decoder2d(wc, z, cfg, tape) -> dL/dz [b,c,t,h,w]."""
+def decoder2d_backward(wc: WeightCache, tape: List[dict], gy: torch.Tensor) -> torch.Tensor:
+    """gy = dL/d(output) [b,out,t,H,W] of engine.constraint_decoder2d / engine.ldm2d_decoder run with `tape` -> dL/dz [b,c,t,h,w]:
+    conv_out, norm_out + SiLU, the levels (ResnetBlocks, Upsample = nearest x2 + 3x3), the mid block, conv_in and -- the legacy LDM
+    checkpoints -- post_quant_conv, backwards.  The layers' names come with the tape (its last entry carries the engine.Spelling)."""
     dtype = wc.p("conv_in.weight").dtype
     last = tape[-1]
     assert last["op"] == "out"
-    B, T, zin = last["B"], last["T"], last["zin"]
-    g = ops.ncdhw_to_ndhwc(gy.contiguous(), 32, dtype)                                           # [b,t,H,W,32], channels 3.. zero
+    B, T, zin, sp = last["B"], last["T"], last["zin"], last["names"]
+    out_ch = wc.p("conv_out.weight").shape[0]
+    if tuple(gy.shape[:3]) != (B, out_ch, T) or out_ch > 32:
+        raise NotImplementedError(f"decoder2d_backward ({sp.name} decoder): cotangent {tuple(gy.shape)} for a decoder with {out_ch} <= 32 "
+                                  f"output channels over {B} x {T} frames")
+    g = ops.ncdhw_to_ndhwc(gy.contiguous(), 32, dtype)                                           # [b,t,H,W,32], channels out_ch.. zero
     g = g.view(B * T, 1, g.shape[2], g.shape[3], 32)
     g = conv_dgrad(wc, g, "conv_out", K2D, P2D, cin_pad=32)                                      # dL/d silu(norm_out(h))
     x = last["x"]
-    g = ops.gn_bwd_input(x, g, unit_tabs(x, last["xp"], 1e-6), *wc.norm("conv_norm_out"), silu=True)
+    g = ops.gn_bwd_input(x, g, unit_tabs(x, last["xp"], 1e-6), *wc.norm(sp.norm_out), silu=True)
     for e in reversed(tape[:-1]):
         if e["op"] == "resnet":
-            g = resnet_backward(wc, g, e)
+            g = resnet_backward(wc, g, e, sp.shortcut[1:])
         elif e["op"] == "attn":
             g = attention_backward(wc, g, e)
-        elif e["op"] == "up":  # Upsample2D: nearest x2, then conv 3x3
+        elif e["op"] == "up":  # Upsample: nearest x2, then conv 3x3
             g = ops.upsample2x_sum(conv_dgrad(wc, g, e["pre"], K2D, P2D))
         else:
             raise AssertionError(e["op"])
-    gz = conv_dgrad(wc, g, "conv_in", K2D, P2D, out_mode=L.OUT_NCDHW)   # [b*t, zin, 1, h, w]
+    if not last.get("post_quant_conv", False):
+        gz = conv_dgrad(wc, g, "conv_in", K2D, P2D, out_mode=L.OUT_NCDHW)                        # [b*t, zin, 1, h, w]
+    else:
+        # conv_in's input gradient keeps the pixel-major layout, channel-padded to the 1x1 kernel's K chunk as the forward pads the
+        # latents; post_quant_conv (zin -> zin) backwards on the flattened pixels; then the narrow gradient goes to NCDHW
+        if zin > 32:
+            raise NotImplementedError(f"decoder2d_backward ({sp.name} decoder): post_quant_conv with {zin} > 32 channels")
+        g = conv_dgrad(wc, g, "conv_in", K2D, P2D, cout_pad=128)                                 # [b*t,1,h,w,128]
+        pq = wc.conv_dgrad("post_quant_conv", K1, cin_pad=128)
+        g = ops.conv(engine._flat(g), pq, cout_pad=32).view(*g.shape[:-1], 32)
+        gz = ops.ndhwc_to_ncdhw(g, zin)
     return gz.view(B, T, zin, gz.shape[3], gz.shape[4]).transpose(1, 2).contiguous()
 
 
-class ConstraintDecoderFn(torch.autograd.Function):
-    """z -> Decoder(z) with the frozen decoder's input gradient as backward (both on the HIP kernels)"""
+constraint_decoder2d_backward = decoder2d_backward  # (either decoder's tape through the one walker)
+ldm2d_decoder_backward = decoder2d_backward
+
+
+class Decoder2DInputGradFn(torch.autograd.Function):
+    """z -> the frozen 2-D decoder `net` (z) with its input gradient as backward (both on the HIP kernels)"""
 
     @staticmethod
     def forward(ctx, z: torch.Tensor, net) -> torch.Tensor:
-        y, ctx.tape = taped(z, lambda tape: engine.constraint_decoder2d(net._cache(), z.detach(), net._cfg, tape))
+        y, ctx.tape = taped(z, lambda tape: type(net)._program(net._cache(), z.detach(), net._cfg, tape))
         begin_node(ctx, net, z, cd=net._cache().compute_dtype)
         return y
 
@@ -115,68 +137,5 @@ class ConstraintDecoderFn(torch.autograd.Function):
         # the tape (block inputs, statistics records, attention operands) is kept until autograd frees the node, so a second
         # backward through it (retain_graph=True, two losses) walks the same tape and gives the same bits
         with backward_pass(ctx, gy):
-            gz = constraint_decoder2d_backward(ctx.net._cache(), ctx.tape, gy)
-        return node_grads(ctx, gz, 1, None)
-
-
-# --------------------------------------------------------------------------------------------------------
-# the frozen LDM (SD2.1-family) image decoder: the same pass over engine.ldm2d_decoder's tape
-# --------------------------------------------------------------------------------------------------------
-def ldm2d_decoder_backward(wc: WeightCache, tape: List[dict], gy: torch.Tensor) -> torch.Tensor:
-    """gy = dL/d(output) [b,out_ch,t,H,W] of engine.ldm2d_decoder(wc, z, cfg, tape) -> dL/dz [b,zc,t,h,w].  Decoder.forward of
-    lvdm/modules/diffusionmodules/model.py:728-772 backwards: conv_out, norm_out + swish, the levels (ResnetBlocks with 1x1
-    nin_shortcut, Upsample = nearest x2 + 3x3), mid (block_2, attn_1, block_1), conv_in and -- legacy=True -- post_quant_conv."""
-    dtype = wc.p("conv_in.weight").dtype
-    last = tape[-1]
-    assert last["op"] == "out"
-    B, T, zin = last["B"], last["T"], last["zin"]
-    out_ch = wc.p("conv_out.weight").shape[0]
-    if tuple(gy.shape[:3]) != (B, out_ch, T) or out_ch > 32:
-        raise NotImplementedError(f"ldm2d_decoder_backward: cotangent {tuple(gy.shape)} for a decoder with {out_ch} <= 32 output "
-                                  f"channels over {B} x {T} frames")
-    g = ops.ncdhw_to_ndhwc(gy.contiguous(), 32, dtype)                                           # [b,t,H,W,32], channels out_ch.. zero
-    g = g.view(B * T, 1, g.shape[2], g.shape[3], 32)
-    g = conv_dgrad(wc, g, "conv_out", K2D, P2D, cin_pad=32)                                      # dL/d swish(norm_out(h))
-    x = last["x"]
-    g = ops.gn_bwd_input(x, g, unit_tabs(x, last["xp"], 1e-6), *wc.norm("norm_out"), silu=True)
-    for e in reversed(tape[:-1]):
-        if e["op"] == "resnet":
-            pre = e["pre"] + "."
-            g = backward.resnet_backward(wc, g, None, block_names(wc, pre, "nin_shortcut"), e["x"], e["xp"], e["h"], e["hp"], 1e-6,
-                                         conv1=(K2D, {}), conv2=(K2D, P2D),
-                                         dgrad1=lambda gh, pre=pre: conv_dgrad(wc, gh, pre + "conv1", K2D, P2D))
-        elif e["op"] == "attn":
-            g = attention_backward(wc, g, e)
-        elif e["op"] == "up":  # Upsample: nearest x2, then conv 3x3
-            g = ops.upsample2x_sum(conv_dgrad(wc, g, e["pre"], K2D, P2D))
-        else:
-            raise AssertionError(e["op"])
-    if not last["post_quant_conv"]:
-        gz = conv_dgrad(wc, g, "conv_in", K2D, P2D, out_mode=L.OUT_NCDHW)                        # [b*t, zin, 1, h, w]
-    else:
-        # conv_in's input gradient keeps the pixel-major layout, channel-padded to the 1x1 kernel's K chunk as the forward pads the
-        # latents; post_quant_conv (zin -> zin) backwards on the flattened pixels; then the narrow gradient goes to NCDHW
-        if zin > 32:
-            raise NotImplementedError(f"ldm2d_decoder_backward: post_quant_conv with {zin} > 32 channels")
-        g = conv_dgrad(wc, g, "conv_in", K2D, P2D, cout_pad=128)                                 # [b*t,1,h,w,128]
-        pq = wc.conv_dgrad("post_quant_conv", K1, cin_pad=128)
-        g = ops.conv(engine._flat(g), pq, cout_pad=32).view(*g.shape[:-1], 32)
-        gz = ops.ndhwc_to_ncdhw(g, zin)
-    return gz.view(B, T, zin, gz.shape[3], gz.shape[4]).transpose(1, 2).contiguous()
-
-
-class LdmDecoderFn(torch.autograd.Function):
-    """z -> the frozen LDM Decoder(z) with its input gradient as backward (both on the HIP kernels)"""
-
-    @staticmethod
-    def forward(ctx, z: torch.Tensor, net) -> torch.Tensor:
-        y, ctx.tape = taped(z, lambda tape: engine.ldm2d_decoder(net._cache(), z.detach(), net._cfg, tape))
-        begin_node(ctx, net, z, cd=net._cache().compute_dtype)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy: torch.Tensor):
-        # (the tape lives as long as the node: a second backward under retain_graph=True walks it again and gives the same bits)
-        with backward_pass(ctx, gy):
-            gz = ldm2d_decoder_backward(ctx.net._cache(), ctx.tape, gy)
+            gz = decoder2d_backward(ctx.net._cache(), ctx.tape, gy)
         return node_grads(ctx, gz, 1, None)

@@ -1,6 +1,7 @@
 """CPU pin of the LAUNCH SEQUENCES of the training path: forward plus backward of every taped network (cvvae_amd/grad.py, grad3d.py,
 discriminator.py, lpips.py over the shared helpers of cvvae_amd/backward.py) must issue the same calls of `cvvae_amd.ops`, in the
-same order, with the same arguments as the recording in tests/golden/backward_launch_trace.json.
+same order, with the same arguments as the recording in tests/golden/backward_launch_trace.json.  The later scenarios pin the
+INFERENCE programs too (eval, no_grad: both 3-D families on a clip and on a single frame, the frozen SD2.1-family 2-D halves).
 
 The tracer runs on the plain-PyTorch emulations of the ops (tests/emu_ops.patched(whole_model=True) plus the discriminator's and
 LPIPS' emulations of tests/test_disc_net_host_logic.py and tests/test_lpips_host_logic.py); no GPU, no library.  It wraps every public
@@ -180,6 +181,52 @@ def _lpips(need0, need1):
     m(x0.requires_grad_(need0), x1.requires_grad_(need1)).sum().backward()
 
 
+LDM = dict(ch=128, out_ch=3, ch_mult=(1, 2, 2), num_res_blocks=1, attn_resolutions=[], in_channels=3, resolution=32, z_channels=4)
+
+
+def _ldm2d_decoder(legacy):
+    """the frozen SD2.1-family decoder: taped forward + input gradient (legacy: with post_quant_conv)"""
+    from cvvae_amd.constraint_ldm import DecoderWith3DWrapper
+    m = _load(DecoderWith3DWrapper(legacy=legacy, **LDM), 5).eval().requires_grad_(False)
+    _step(m, seeded_input((2, 4, 1, 5, 4), 9))
+
+
+def _ldm2d_encoder(legacy):
+    from cvvae_amd.constraint_ldm import EncoderWith3DWrapper
+    m = _load(EncoderWith3DWrapper(legacy=legacy, **LDM), 6).eval()
+    with torch.no_grad():
+        m(seeded_input((1, 3, 2, 16, 24), 10))
+
+
+def _inference(model):
+    """the untaped programs: encode + decode of a clip, then of a single frame (the temporally folded path)"""
+    model.eval()
+    with torch.no_grad():
+        for shape in ((1, 3, 5, 16, 24), (1, 3, 1, 16, 24)):
+            model.decode(model.encode(seeded_input(shape, 12)).latent_dist.mode())
+
+
+def sd3_inference():
+    import cvvae_amd
+    _inference(_load(cvvae_amd.CVVAESD3Model(**SD3), 7))
+
+
+def vae3d_inference():
+    import cvvae_amd
+    _inference(_load(cvvae_amd.CVVAEModel(causal_encoder=True, **V3), 9))
+
+
+def sd3_no_mid_attention():
+    import cvvae_amd
+    from cvvae_amd.constraint import DecoderWith3DWrapper
+    m = _load(cvvae_amd.CVVAESD3Model(mid_block_add_attention=False, **SD3), 7).eval()
+    with torch.no_grad():
+        m.encoder(seeded_input((1, 3, 5, 16, 24), 11))
+        m.decoder(seeded_input((1, 16, 3, 4, 6), 13))
+    d = _load(DecoderWith3DWrapper(**dict(C2D, mid_block_add_attention=False)), 5).eval().requires_grad_(False)
+    _step(d, seeded_input((2, 16, 1, 5, 4), 9))
+
+
 SCENARIOS = {
     "sd3_encoder": sd3_encoder,
     "sd3_decoder": sd3_decoder,
@@ -195,6 +242,13 @@ SCENARIOS = {
     "lpips_input": lambda: _lpips(True, False),
     "lpips_target": lambda: _lpips(False, True),
     "lpips_both": lambda: _lpips(True, True),
+    "ldm2d_decoder_legacy": lambda: _ldm2d_decoder(True),
+    "ldm2d_decoder_plain": lambda: _ldm2d_decoder(False),
+    "ldm2d_encoder_legacy": lambda: _ldm2d_encoder(True),
+    "ldm2d_encoder_plain": lambda: _ldm2d_encoder(False),
+    "sd3_inference": sd3_inference,
+    "vae3d_inference": vae3d_inference,
+    "sd3_no_mid_attention": sd3_no_mid_attention,
 }
 
 

@@ -96,7 +96,7 @@ def test_ldm_decoder_node_under_autograd_and_its_refusals():
     cot = seeded_input((2, 3, 48, 32), int(fix["cot_seed"]))
     with emu_ops.patched(whole_model=True):
         y = m(z)
-        assert y.requires_grad and type(y.grad_fn.next_functions[0][0]).__name__.startswith("LdmDecoderFn")  # (under the 4-D squeeze)
+        assert y.requires_grad and type(y.grad_fn.next_functions[0][0]).__name__.startswith("Decoder2DInputGradFn")  # (under the 4-D squeeze)
         loss = (y * cot).sum()
         loss.backward(retain_graph=True)
         g1 = z.grad.clone()
