@@ -81,7 +81,17 @@ class FrameMap(ctypes.Structure):
                 ("index", ctypes.POINTER(ctypes.c_int32))]
 
 
-_vp, _i32, _i64, _f32, _f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double
+CLIP_NCTHW, CLIP_THWC_U8 = 0, 1  # cvvae_clip_view.layout
+
+
+class ClipView(ctypes.Structure):
+    """mirror of `cvvae_clip_view` (include/cvvae.h)"""
+
+    _fields_ = [("layout", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("sb", ctypes.c_int64), ("sc", ctypes.c_int64), ("st", ctypes.c_int64), ("sy", ctypes.c_int64)]
+
+
+_vp, _i32, _i64, _f32, _f64 =ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 
 # name -> (restype, argtypes): every symbol include/cvvae.h declares
 PROTOTYPES = {
@@ -160,14 +170,18 @@ PROTOTYPES = {
     "cvvae_mt_scale": (_i32, [_i32, _vp, _vp, _i64, _vp, _vp]),
     "cvvae_mt_adamw": (_i32, [_i32, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _vp, _vp]),
     "cvvae_mt_ema": (_i32, [_i32, _vp, _vp, _i64, _f32, _vp]),
+    "cvvae_frame_metrics_workspace_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32, _i32]),
+    "cvvae_frame_metrics": (_i32, [_vp, ctypes.POINTER(ClipView), _vp, ctypes.POINTER(ClipView), _i32, _i32, _i32, _i32, _i32, _i32,
+                                   _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
 
 
-# translation units whose kernels only run in training (weight gradients, channel sums, their reductions): no launch of an
+# translation units whose kernels only run in training (weight gradients, channel sums, their reductions) or in scoring a
+# reconstruction (metrics_kernels.hip): no launch of an
 # encode / decode step comes from them, so the counters of the inference bench do not go stale when they change
-TRAINING_ONLY_SOURCES = ("wgrad_kernel.hip", "loss_kernels.hip", "disc_kernels.hip", "optim_kernels.hip")
+TRAINING_ONLY_SOURCES = ("wgrad_kernel.hip", "loss_kernels.hip", "disc_kernels.hip", "optim_kernels.hip", "metrics_kernels.hip")
 
 
 def source_fingerprint() -> str:

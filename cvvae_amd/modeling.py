@@ -916,6 +916,24 @@ class _CVVAEBase(nn.Module):
         with torch.cuda.device(x.device):  # (the launch goes to x's device whatever the caller's current device is)
             return ops.ncdhw_to_frames_u8(x.contiguous())
 
+    @torch.no_grad()
+    def score_reconstruction_u8(self, frames: torch.Tensor, size: Optional[Tuple[int, int]] = None, meter=None) -> dict:
+        """The scripts' round trip with a verdict: `encode_frames_u8(frames, size=size)` -> `.latent_dist.mode()` ->
+        `decode_to_frames_u8`, scored per frame against the frames the encoder saw (resized when `size` is given, truncated to
+        1 + (T-1)//4*4).  -> {"sse", "psnr", "ssim"} device tensors [1,T'] (cvvae_amd.metrics.frame_metrics), plus "lpips" when
+        `meter` (a metrics.ReconstructionMeter, updated with this clip) carries the network.  The scoring adds no host synchronisation to the round trip's."""
+        from . import metrics
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+            raise ValueError(f"expected uint8 frames [T,H,W,3], got {frames.dtype} {tuple(frames.shape)}")
+        with torch.cuda.device(frames.device):
+            if size is not None:
+                frames = ops.resize_frames_u8(frames.contiguous(), size)
+            seen = frames[:1 + (frames.shape[0] - 1) // 4 * 4]
+            recon = self.decode_to_frames_u8(self.encode_frames_u8(seen).latent_dist.mode())
+            if meter is not None:
+                return meter.update(seen, recon)
+            return metrics.frame_metrics(seen, recon)
+
     def forward(self, sample: torch.Tensor, sample_posterior: bool = False, return_dict: bool = True,
                 generator: Optional[torch.Generator] = None, num_frames: Optional[int] = None
                 ) -> Union[DecoderOutput, Tuple[torch.Tensor]]:

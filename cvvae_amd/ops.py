@@ -909,6 +909,76 @@ def ncdhw_to_frames_u8(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ---- per-frame reconstruction metrics (include/cvvae.h cvvae_frame_metrics; cvvae_amd/metrics.py) ----
+def clip_extents(t: torch.Tensor) -> Tuple[int, int, int, int]:
+    """(B, T, H, W) of an operand of frame_metrics: uint8 frames [T,H,W,3] (B = 1) or an fp16 / bf16 / fp32 clip [B,3,T,H,W]"""
+    if t.dtype == torch.uint8:
+        if t.dim() != 4 or t.shape[-1] != 3:
+            raise ValueError(f"frame_metrics: uint8 frames are [T,H,W,3]; got {tuple(t.shape)}")
+        return (1,) + tuple(t.shape[:3])
+    if t.dtype not in _DT:
+        raise ValueError(f"frame_metrics: operands are uint8 frames or fp16 / bf16 / fp32 clips; got {t.dtype}")
+    if t.dim() != 5 or t.shape[1] != 3:
+        raise ValueError(f"frame_metrics: float clips are [B,3,T,H,W]; got {tuple(t.shape)}")
+    return (t.shape[0],) + tuple(t.shape[2:])
+
+
+def check_metric_operands(a: torch.Tensor, b: torch.Tensor, want_ssim: bool) -> Tuple[int, int, int, int]:
+    """the ValueErrors of frame_metrics, raised before anything touches the device -> (B, T, H, W)"""
+    da, db = clip_extents(a), clip_extents(b)
+    if da != db:
+        if da[1:] == db[1:]:
+            raise ValueError(f"frame_metrics: uint8 frames are one clip (B = 1); the other operand has B = {max(da[0], db[0])}")
+        raise ValueError(f"frame_metrics: operands of extents (B,T,H,W) = {da} and {db}")
+    if a.device != b.device:
+        raise ValueError(f"frame_metrics: operands on {a.device} and {b.device}")
+    if min(da) < 1:
+        raise ValueError(f"frame_metrics: empty operand, (B,T,H,W) = {da}")
+    if want_ssim and min(da[2:]) < 11:
+        raise ValueError(f"frame_metrics: SSIM's 11-tap window needs H, W >= 11; got {da[2]} x {da[3]}")
+    return da
+
+
+def _clip_view(t: torch.Tensor) -> Tuple[torch.Tensor, "L.ClipView"]:
+    """an operand of frame_metrics -> (the tensor the kernel reads, its cvvae_clip_view).  uint8 frames whose [W,3] rows are contiguous
+    and float clips whose innermost stride is 1 are read in place (a frame slice, a row crop, a window, one half of a cat); any other
+    layout gets one .contiguous() copy."""
+    v = L.ClipView()
+    if t.dtype == torch.uint8:
+        W = t.shape[2]
+        if t.stride()[2:] != (3, 1) or t.stride(1) < 3 * W:
+            t = t.contiguous()
+        v.layout, v.dtype, v.sb, v.sc, v.st, v.sy = L.CLIP_THWC_U8, 0, 0, 1, t.stride(0), t.stride(1)
+        return t, v
+    W = t.shape[4]
+    if t.stride(4) != 1 or t.stride(3) < W:
+        t = t.contiguous()
+    sb, sc, st, sy, _ = t.stride()
+    v.layout, v.dtype, v.sb, v.sc, v.st, v.sy = L.CLIP_NCTHW, _DT[t.dtype], sb, sc, st, sy
+    return t, v
+
+
+def frame_metrics(a: torch.Tensor, b: torch.Tensor, quantize: bool = True, want_ssim: bool = True
+                  ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """per-frame metrics of two clips on the 8-bit scale -> (sse fp64 [B,T], psnr fp32 [B,T], ssim fp32 [B,T] or None), one pass over
+    both operands on the HIP kernel.  a / b: independently uint8 frames [T,H,W,3] (B = 1) or a float clip [B,3,T,H,W] in [-1,1];
+    quantize: float values go to the byte ncdhw_to_frames_u8 would store (else (clamp(x,-1,1)+1)*127.5 in fp32).  No host sync."""
+    lib = L.load()
+    _need_gpu(a)
+    _need_gpu(b)
+    B, T, H, W = check_metric_operands(a, b, want_ssim)
+    a, va = _clip_view(a)
+    b, vb = _clip_view(b)
+    ws = torch.empty(max(int(lib.cvvae_frame_metrics_workspace_bytes(B, T, H, W, int(want_ssim))), 16), dtype=torch.uint8, device=a.device)
+    sse = torch.empty((B, T), dtype=torch.float64, device=a.device)
+    psnr = torch.empty((B, T), dtype=torch.float32, device=a.device)
+    ssim = torch.empty((B, T), dtype=torch.float32, device=a.device) if want_ssim else None
+    L.check(lib.cvvae_frame_metrics(a.data_ptr(), ctypes.byref(va), b.data_ptr(), ctypes.byref(vb), B, T, H, W, int(bool(quantize)),
+                                    int(bool(want_ssim)), sse.data_ptr(), psnr.data_ptr(), ssim.data_ptr() if want_ssim else None,
+                                    ws.data_ptr(), _stream(a)), "cvvae_frame_metrics")
+    return sse, psnr, ssim
+
+
 # ---- the passes around the VGG16 convolutions of the LPIPS perceptual loss (include/cvvae.h ABI 14; cvvae_amd/lpips.py) ----
 def lpips_scale_in(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, cpad: int, dtype: torch.dtype,
                    out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -674,6 +674,41 @@ int cvvae_mt_adamw(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_t
 int cvvae_mt_ema(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float one_minus_decay,
                  void* stream);
 
+/*
+ * Per-frame reconstruction metrics of two clips on the 8-bit scale, data_range = 255 (cvvae_amd/metrics.py; csrc/metrics_kernels.hip):
+ * the sum of squared errors, PSNR, and the Gaussian-window SSIM of Wang et al. (11 taps, sigma 1.5, window normalised to sum 1 and
+ * applied separably, "valid" positions only, population covariance, C1 = 2.55^2, C2 = 7.65^2, mean over the 3 channels and the
+ * (H-10) x (W-10) positions).  Additions to ABI 14: no existing entry point or struct changed, so the version number stays.
+ *
+ * An operand is uint8 frames [T][H][W][3] (CVVAE_CLIP_THWC_U8; B = 1; st, sy in bytes, a row is 3W contiguous bytes, no alignment asked)
+ * or a float clip [B][3][T][H][W] nominally in [-1, 1] (CVVAE_CLIP_NCTHW; dtype CVVAE_F16 / BF16 / F32; sb, sc, st, sy in elements, a row
+ * is W contiguous elements).  The two operands are chosen independently and both are read in place, once.  A float value goes to the
+ * 8-bit scale as the byte cvvae_ncdhw_to_frames_u8 would store for it (quantize != 0: clamp, + 1 and * 127.5 each rounded to the clip's
+ * dtype, truncation) or as (clamp(x,-1,1) + 1) * 127.5 in fp32 (quantize == 0).  NaN is outside the contract.
+ *
+ * Per frame f = b * T + t:  sse[f] = sum (u - v)^2 over its 3HW samples, fp64 (exact whenever both operands are on integer values);
+ * psnr[f] = (float)(10 log10(65025 * 3HW / sse)), +inf where sse == 0;  ssim[f] (want_ssim != 0, needs H, W >= 11).
+ * Everything behind the conversion to the 8-bit scale is fp64 (window sums as FMA chains over exact products), so E[x^2] - mu^2 does
+ * not cancel against C2, and a clip against itself gives ssim == 1.0f exactly.  Two launches: one workgroup per 16 x 32 tile of map
+ * positions writes one (SSIM sum, SSE) partial to `workspace` (cvvae_frame_metrics_workspace_bytes; 8-byte aligned); one wave per
+ * frame merges them in a fixed order.  Nothing is atomic: the results are a function of the values alone, whatever the strides.
+ *
+ * Before any launch.  CVVAE_EINVAL: a NULL a, b, view, sse, psnr or workspace (ssim too when want_ssim), a misaligned output or workspace,
+ * a non-positive extent, a negative stride, sy smaller than a row.  CVVAE_EUNSUPPORTED: an unknown layout or dtype, a THWC operand with
+ * B != 1, want_ssim with H < 11 or W < 11, H or W > 2^20, B * T > 65535.  The workspace-bytes function is pure host code and returns 0
+ * for extents the call would refuse.
+ */
+enum { CVVAE_CLIP_NCTHW = 0, CVVAE_CLIP_THWC_U8 = 1 };
+typedef struct cvvae_clip_view {
+  int32_t layout; /* CVVAE_CLIP_* */
+  int32_t dtype;  /* CVVAE_F16 / CVVAE_BF16 / CVVAE_F32; NCTHW only */
+  int64_t sb, sc, st, sy; /* strides of batch, channel, frame, row (THWC reads st and sy only) */
+} cvvae_clip_view;
+size_t cvvae_frame_metrics_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t W, int32_t want_ssim);
+int cvvae_frame_metrics(const void* a, const cvvae_clip_view* va, const void* b, const cvvae_clip_view* vb, int32_t B, int32_t T,
+                        int32_t H, int32_t W, int32_t quantize, int32_t want_ssim, double* sse, float* psnr, float* ssim,
+                        void* workspace, void* stream);
+
 int cvvae_abi_version(void);
 /* name of the kernel instance cvvae_conv_fwd would launch for d (for profiling reports); NULL if unsupported */
 const char* cvvae_conv_kernel_name(const cvvae_conv_desc* d);
