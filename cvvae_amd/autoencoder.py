@@ -1,0 +1,623 @@
+"""The training engines of lvdm/models/autoencoder.py as plain `nn.Module`s: one object owns the networks, the regulariser, the loss,
+the two optimizers, their schedulers and the EMA, and `training_step(batch, batch_idx)` runs one whole CV-VAE iteration on the HIP
+kernels.  Reachable as `lvdm.models.autoencoder` (the training YAML's `model.target`).
+
+Classes, with the reference's constructor parameters, defaults, submodule names (`encoder`, `decoder`, `loss`, `regularization`,
+`constraint_encoder`, `constraint_decoder`, `model_ema`: the `state_dict()` keys of a Lightning checkpoint) and methods:
+
+  AbstractAutoencoder                        :30-135    EMA, apply_ckpt, the optimizer / scheduler factories
+  AutoencodingEngine                         :138-543   encoder + regulariser + decoder + loss
+  AutoencodingEngineWithLatentConstraint     :1002-1219 + a frozen 2-D decoder on the 3-D latents (the shipped YAML)
+  AutoencodingEngineWithAllConstraint        :1457-1694 + a frozen 2-D encoder whose latents are decoded next to the 3-D ones
+
+What pytorch_lightning did for the reference is stated here (nothing of it is imported):
+
+  learning_rate     an attribute the caller sets (`build_from_config` sets it to the YAML's `base_learning_rate`)
+  optimizers(), lr_schedulers()   what `configure_optimizers` built, created on the first `training_step`
+  global_step       counts `opt.step()` calls
+  toggle_model      around the loss and the backward, every parameter that belongs only to the OTHER optimizer has requires_grad
+                    switched off; restored afterwards, on an exception too
+  clip_gradients    to 1.0 by norm: an optimizer with `max_grad_norm` set (cvvae_amd.optim.AdamW) clips inside its step, any other
+                    goes through cvvae_amd.optim.clip_grad_norm_
+  log / log_dict    fill `self.last_logs`, a dict of 0-dim device tensors, handed to the optional `self.log_fn(logs, global_step)`
+
+`training_step` itself never reads a device value back (tests/test_gpu_train_engine.py runs it with bf16 networks under torch's
+synchronisation check; an fp32 network's weight packing reads max|w| back after each step: ops._wscale, split precision).
+`on_train_batch_end` is the EMA update, as in the reference a separate call.
+
+Reproducibility: `self.sample_generator` is passed as `generator=` to a regulariser whose forward takes it (the posterior noise; a
+device generator) and to a loss whose forward takes it (the CPU draw of the "random" target frames; handed over when it is a CPU
+generator -- a device generator cannot seed a CPU draw, which then uses torch's global generator as the reference does);
+`self.frame_indices` is passed as `frame_indices=` the same way.
+
+One deviation, on purpose: the reference creates `LitEma(self)` in the base constructor, before any network exists, so its EMA
+holds no shadow and the first update raises KeyError.  Here `model_ema` is built when the constructor has made its networks and
+applied the `trainable` switch, under the same name and with the same buffer names, so `ema_decay` works.
+
+`log_images` returns the reference's keys; every tensor in it comes out of `ops.recon_panels` (csrc/panel_kernels.hip), one pass
+over the two clips per call, under `torch.no_grad()`.
+
+Not built: AutoencodingEngineWithEncoderConstraint (its loss in the reference reads `self.logvar_2d`, which that class never
+creates), the legacy / VQ engines of that file, a Lightning adapter, DDP, the data module.
+"""
+import inspect
+import re
+import warnings
+from contextlib import contextmanager
+from typing import Any, Dict, List, Optional, Tuple, Union
+
+import torch
+import torch.nn as nn
+
+from lvdm.modules.ema import LitEma
+from lvdm.util import default, get_obj_from_str, instantiate_from_config
+
+from . import ops
+from . import optim as _optim
+
+__all__ = ["AbstractAutoencoder", "AutoencodingEngine", "AutoencodingEngineWithLatentConstraint",
+           "AutoencodingEngineWithAllConstraint", "build_from_config"]
+
+_CONSTANT = {"target": "lvdm.lr_scheduler.get_scheduler", "params": {"name": "constant"}}
+
+
+def _takes(module: nn.Module, name: str) -> bool:
+    try:
+        return name in inspect.signature(module.forward).parameters
+    except (TypeError, ValueError):
+        return False
+
+
+class AbstractAutoencoder(nn.Module):
+    def __init__(self, ema_decay: Union[None, float] = None, monitor: Union[None, str] = None, input_key: str = "jpg"):
+        super().__init__()
+        self.input_key = input_key
+        self.use_ema = ema_decay is not None
+        self.ema_decay = ema_decay
+        if monitor is not None:
+            self.monitor = monitor
+        self.automatic_optimization = False
+        # what the trainer held
+        self.learning_rate: Optional[float] = None
+        self.global_step = 0
+        self.last_logs: Dict[str, torch.Tensor] = {}
+        self.log_fn = None
+        self.sample_generator: Optional[torch.Generator] = None
+        self.frame_indices = None
+        self.validation_meter = None
+        self._opts: Optional[list] = None
+        self._sches: Optional[list] = None
+
+    def _build_ema(self) -> None:
+        """(re)build `model_ema` over the parameters that require grad NOW: called by a constructor once its networks exist"""
+        if self.use_ema:
+            if "model_ema" in self._modules:
+                del self._modules["model_ema"]
+            self.model_ema = LitEma(self, decay=self.ema_decay)
+
+    def apply_ckpt(self, ckpt: Union[None, str, dict]):
+        if ckpt is None:
+            return
+        if isinstance(ckpt, str):
+            if ckpt.endswith("ckpt"):
+                ckpt = torch.load(ckpt, map_location="cpu")["state_dict"]
+            elif ckpt.endswith("safetensors"):
+                from safetensors.torch import load_file
+                ckpt = load_file(ckpt)
+            else:
+                raise NotImplementedError
+        missing, unexpected = self.load_state_dict(ckpt, strict=False)
+        print(f"Restored vae weights with {len(missing)} missing and {len(unexpected)} unexpected keys")
+        if len(missing) > 0:
+            print(f"Missing Keys: {missing}")
+        if len(unexpected) > 0:
+            print(f"Unexpected Keys: {unexpected}")
+
+    def get_input(self, batch) -> Any:
+        raise NotImplementedError()
+
+    def on_train_batch_end(self, *args, **kwargs):
+        if self.use_ema:
+            self.model_ema(self)
+
+    @contextmanager
+    def ema_scope(self, context=None):
+        if self.use_ema:
+            self.model_ema.store(self.parameters())
+            self.model_ema.copy_to(self)
+        try:
+            yield None
+        finally:
+            if self.use_ema:
+                self.model_ema.restore(self.parameters())
+
+    def encode(self, *args, **kwargs) -> torch.Tensor:
+        raise NotImplementedError("encode()-method of abstract base class called")
+
+    def decode(self, *args, **kwargs) -> torch.Tensor:
+        raise NotImplementedError("decode()-method of abstract base class called")
+
+    def instantiate_optimizer_from_config(self, params, lr, cfg):
+        return get_obj_from_str(cfg["target"])(params, lr=lr, **cfg.get("params", dict()))
+
+    def instantiate_scheduler_from_config(self, optimizer, cfg):
+        return get_obj_from_str(cfg["target"])(optimizer=optimizer, **cfg.get("params", dict()))
+
+    def configure_optimizers(self) -> Any:
+        raise NotImplementedError()
+
+    # ---- the trainer's side ----
+    def _configured(self) -> Tuple[list, list]:
+        if self._opts is None:
+            opts, sches = self.configure_optimizers()
+            self._opts, self._sches = list(opts), list(sches)
+        return self._opts, self._sches
+
+    def optimizers(self):
+        opts, _ = self._configured()
+        return opts[0] if len(opts) == 1 else opts
+
+    def lr_schedulers(self):
+        _, sches = self._configured()
+        return sches[0] if len(sches) == 1 else sches
+
+    def log(self, name: str, value, **_) -> None:
+        self.last_logs[name] = value
+
+    def log_dict(self, dictionary: Dict[str, Any], **_) -> None:
+        self.last_logs.update(dictionary)
+
+    def manual_backward(self, loss: torch.Tensor) -> None:
+        loss.backward()
+
+    @contextmanager
+    def toggle_model(self, optimizer):
+        """requires_grad off for every parameter that belongs only to another optimizer; restored on the way out"""
+        opts, _ = self._configured()
+        state: Dict[nn.Parameter, bool] = {}
+        for opt in opts:
+            for group in opt.param_groups:
+                for p in group["params"]:
+                    if p not in state:
+                        state[p] = p.requires_grad
+                        p.requires_grad = False
+        for group in optimizer.param_groups:
+            for p in group["params"]:
+                p.requires_grad = state[p]
+        try:
+            yield
+        finally:
+            for p, flag in state.items():
+                p.requires_grad = flag
+
+    def clip_gradients(self, optimizer, gradient_clip_val: float = 1.0, gradient_clip_algorithm: str = "norm") -> None:
+        if gradient_clip_algorithm != "norm":
+            raise NotImplementedError(f"gradient_clip_algorithm={gradient_clip_algorithm!r}: only 'norm'")
+        if getattr(optimizer, "max_grad_norm", None) is not None:
+            return  # cvvae_amd.optim.AdamW(max_grad_norm=...): the step reads the clip coefficient from device memory
+        _optim.clip_grad_norm_([p for g in optimizer.param_groups for p in g["params"]], gradient_clip_val)
+
+
+class AutoencodingEngine(AbstractAutoencoder):
+    def __init__(
+        self,
+        *args,
+        encoder_config: Dict,
+        decoder_config: Dict,
+        loss_config: Dict,
+        regularizer_config: Dict,
+        optimizer_config: Union[Dict, None] = None,
+        lr_g_factor: float = 1.0,
+        lr_g_scheduler_config: Optional[dict] = None,
+        lr_d_scheduler_config: Optional[dict] = None,
+        trainable_ae_params: Optional[List[List[str]]] = None,
+        ae_optimizer_args: Optional[List[dict]] = None,
+        trainable_disc_params: Optional[List[List[str]]] = None,
+        disc_optimizer_args: Optional[List[dict]] = None,
+        disc_start_iter: int = 0,
+        diff_boost_factor: float = 3.0,
+        ckpt_engine: Union[None, str, dict] = None,
+        ckpt_path: Optional[str] = None,
+        additional_decode_keys: Optional[List[str]] = None,
+        trainable: Union[bool, str] = True,
+        **kwargs,
+    ):
+        super().__init__(*args, **kwargs)
+        self.encoder: nn.Module = instantiate_from_config(encoder_config)
+        self.decoder: nn.Module = instantiate_from_config(decoder_config)
+        self.loss: nn.Module = instantiate_from_config(loss_config)
+        self.regularization: nn.Module = instantiate_from_config(regularizer_config)
+        self.optimizer_config = default(optimizer_config, {"target": "torch.optim.Adam"})
+        self.lr_g_scheduler_config = default(lr_g_scheduler_config, dict(_CONSTANT))
+        self.lr_d_scheduler_config = default(lr_d_scheduler_config, dict(_CONSTANT))
+        self.diff_boost_factor = diff_boost_factor
+        self.disc_start_iter = disc_start_iter
+        self.lr_g_factor = lr_g_factor
+        self.trainable_ae_params = trainable_ae_params
+        if self.trainable_ae_params is not None:
+            self.ae_optimizer_args = default(ae_optimizer_args, [{} for _ in range(len(self.trainable_ae_params))])
+            assert len(self.ae_optimizer_args) == len(self.trainable_ae_params)
+        else:
+            self.ae_optimizer_args = [{}]
+        self.trainable_disc_params = trainable_disc_params
+        if self.trainable_disc_params is not None:
+            self.disc_optimizer_args = default(disc_optimizer_args, [{} for _ in range(len(self.trainable_disc_params))])
+            assert len(self.disc_optimizer_args) == len(self.trainable_disc_params)
+        else:
+            self.disc_optimizer_args = [{}]
+        if ckpt_path is not None:
+            assert ckpt_engine is None, "Can't set ckpt_engine and ckpt_path"
+            warnings.warn("Checkpoint path is deprecated, use `ckpt_engine` instead")
+        self.additional_decode_keys = set(default(additional_decode_keys, []))
+        assert trainable in [True, False, "decoder", "encoder"], f"trainable ({trainable}) must in [True, False, decoder,encoder]"
+        if not trainable:
+            self.requires_grad_(False)
+        elif trainable == "decoder":
+            self.encoder.requires_grad_(False)
+        elif trainable == "encoder":
+            self.decoder.requires_grad_(False)
+        self._reg_takes_generator = _takes(self.regularization, "generator")
+        self._loss_takes_generator = _takes(self.loss, "generator")
+        self._loss_takes_frame_indices = _takes(self.loss, "frame_indices")
+        self._build_ema()
+        self.apply_ckpt(default(ckpt_path, ckpt_engine))
+
+    def get_input(self, batch: Dict) -> torch.Tensor:
+        return batch[self.input_key]
+
+    def get_autoencoder_params(self) -> list:
+        params = []
+        if hasattr(self.loss, "get_trainable_autoencoder_parameters"):
+            params += list(self.loss.get_trainable_autoencoder_parameters())
+        if hasattr(self.regularization, "get_trainable_parameters"):
+            params += list(self.regularization.get_trainable_parameters())
+        params = params + list(self.encoder.parameters())
+        params = params + list(self.decoder.parameters())
+        return params
+
+    def get_discriminator_params(self) -> list:
+        if hasattr(self.loss, "get_trainable_parameters"):
+            return list(self.loss.get_trainable_parameters())
+        return []
+
+    def get_last_layer(self):
+        return self.decoder.get_last_layer()
+
+    def _regularize(self, z: torch.Tensor) -> Tuple[torch.Tensor, dict]:
+        if self._reg_takes_generator:
+            return self.regularization(z, generator=self.sample_generator)
+        return self.regularization(z)
+
+    def encode(self, x: torch.Tensor, return_reg_log: bool = False, unregularized: bool = False
+               ) -> Union[torch.Tensor, Tuple[torch.Tensor, dict]]:
+        z = self.encoder(x)
+        if unregularized:
+            return z, dict()
+        z, reg_log = self._regularize(z)
+        if return_reg_log:
+            return z, reg_log
+        return z
+
+    def decode(self, z: torch.Tensor, **kwargs) -> torch.Tensor:
+        return self.decoder(z, **kwargs)
+
+    def forward(self, x: torch.Tensor, **additional_decode_kwargs) -> Tuple[torch.Tensor, torch.Tensor, dict]:
+        z, reg_log = self.encode(x, return_reg_log=True)
+        dec = self.decode(z, **additional_decode_kwargs)
+        return z, dec, reg_log
+
+    # ---- one iteration ----
+    def _extra_info(self, z, optimizer_idx: int, split: str, regularization_log: dict) -> dict:
+        if not hasattr(self.loss, "forward_keys"):
+            return dict()
+        info = {"z": z, "optimizer_idx": optimizer_idx, "global_step": self.global_step, "last_layer": self.get_last_layer(),
+                "split": split, "regularization_log": regularization_log, "autoencoder": self}
+        return {k: info[k] for k in self.loss.forward_keys}
+
+    def _loss_seeds(self) -> dict:
+        kw = {}
+        g = self.sample_generator
+        if self._loss_takes_generator and g is not None and g.device.type == "cpu":
+            kw["generator"] = g
+        if self._loss_takes_frame_indices and self.frame_indices is not None:
+            kw["frame_indices"] = self.frame_indices
+        return kw
+
+    def _networks(self, x: torch.Tensor, **additional_decode_kwargs) -> Tuple[torch.Tensor, tuple, dict]:
+        """-> (z, what the loss takes behind the inputs, regularization_log)"""
+        z, xrec, regularization_log = self(x, **additional_decode_kwargs)
+        return z, (xrec,), regularization_log
+
+    def inner_training_step(self, batch: dict, batch_idx: int, optimizer_idx: int = 0) -> torch.Tensor:
+        x = self.get_input(batch)
+        additional_decode_kwargs = {key: batch[key] for key in self.additional_decode_keys.intersection(batch)}
+        z, recs, regularization_log = self._networks(x, **additional_decode_kwargs)
+        extra_info = self._extra_info(z, optimizer_idx, "train", regularization_log)
+        if optimizer_idx == 0:
+            out_loss = self.loss(x, *recs, **extra_info, **self._loss_seeds())
+            if isinstance(out_loss, tuple):
+                aeloss, log_dict_ae = out_loss
+            else:
+                aeloss = out_loss
+                log_dict_ae = {"train/loss/rec": aeloss.detach()}
+            self.log_dict(log_dict_ae)
+            self.log("loss", aeloss.mean().detach())
+            return aeloss
+        elif optimizer_idx == 1:
+            discloss, log_dict_disc = self.loss(x, *recs, **extra_info, **self._loss_seeds())
+            self.log_dict(log_dict_disc)
+            return discloss
+        raise NotImplementedError(f"Unknown optimizer {optimizer_idx}")
+
+    def training_step(self, batch: dict, batch_idx: int):
+        opts, sches = self._configured()
+        optimizer_idx = batch_idx % len(opts)
+        if self.global_step < self.disc_start_iter:
+            optimizer_idx = 0
+        opt = opts[optimizer_idx]
+        self.last_logs = {}
+        opt.zero_grad()
+        with self.toggle_model(opt):
+            loss = self.inner_training_step(batch, batch_idx, optimizer_idx=optimizer_idx)
+            self.manual_backward(loss)
+            self.clip_gradients(opt, gradient_clip_val=1.0, gradient_clip_algorithm="norm")
+        opt.step()
+        self.global_step += 1
+        with warnings.catch_warnings():  # (the scheduler of the optimizer that did not step this iteration steps too, as in the reference)
+            warnings.filterwarnings("ignore", message=r"Detected call of `lr_scheduler.step\(\)` before `optimizer.step\(\)`")
+            for sche in sches:
+                sche.step()
+        if self.log_fn is not None:
+            self.log_fn(self.last_logs, self.global_step)
+        return loss.detach()
+
+    def validation_step(self, batch: dict, batch_idx: int) -> Dict:
+        """both passes run in eval() mode under no_grad, as the trainer's validation loop ran them; the mode is put back"""
+        was_training = self.training
+        self.eval()
+        try:
+            log_dict = self._validation_step(batch, batch_idx)
+            with self.ema_scope():
+                log_dict_ema = self._validation_step(batch, batch_idx, postfix="_ema")
+                log_dict.update(log_dict_ema)
+        finally:
+            self.train(was_training)
+        return log_dict
+
+    def _first_reconstruction(self, recs: tuple) -> torch.Tensor:
+        return recs[0]
+
+    @torch.no_grad()
+    def _validation_step(self, batch: dict, batch_idx: int, postfix: str = "") -> Dict:
+        x = self.get_input(batch)
+        z, recs, regularization_log = self._networks(x)
+        extra_info = self._extra_info(z, 0, "val" + postfix, regularization_log)
+        out_loss = self.loss(x, *recs, **extra_info, **self._loss_seeds())
+        if isinstance(out_loss, tuple):
+            aeloss, log_dict_ae = out_loss
+        else:
+            aeloss = out_loss
+            log_dict_ae = {f"val{postfix}/loss/rec": aeloss.detach()}
+        full_log_dict = log_dict_ae
+        if "optimizer_idx" in extra_info:
+            extra_info["optimizer_idx"] = 1
+            discloss, log_dict_disc = self.loss(x, *recs, **extra_info, **self._loss_seeds())
+            full_log_dict.update(log_dict_disc)
+        self.log(f"val{postfix}/loss/rec", log_dict_ae[f"val{postfix}/loss/rec"])
+        self.log_dict(full_log_dict)
+        if self.validation_meter is not None and not postfix:
+            self.validation_meter.update(x, self._first_reconstruction(recs))
+        return full_log_dict
+
+    def get_param_groups(self, parameter_names: List[List[str]], optimizer_args: List[dict]) -> Tuple[List[Dict[str, Any]], int]:
+        groups = []
+        num_params = 0
+        for names, args in zip(parameter_names, optimizer_args):
+            params = []
+            for pattern_ in names:
+                pattern_params = []
+                pattern = re.compile(pattern_)
+                for p_name, param in self.named_parameters():
+                    if re.match(pattern, p_name):
+                        pattern_params.append(param)
+                        num_params += param.numel()
+                if len(pattern_params) == 0:
+                    warnings.warn(f"Did not find parameters for pattern {pattern_}")
+                params.extend(pattern_params)
+            groups.append({"params": params, **args})
+        return groups, num_params
+
+    def configure_optimizers(self) -> Tuple[list, list]:
+        if self.learning_rate is None:
+            raise RuntimeError("learning_rate is not set: assign `engine.learning_rate` (build_from_config sets it to base_learning_rate)")
+        if self.trainable_ae_params is None:
+            ae_params = self.get_autoencoder_params()
+        else:
+            ae_params, _ = self.get_param_groups(self.trainable_ae_params, self.ae_optimizer_args)
+        if self.trainable_disc_params is None:
+            disc_params = self.get_discriminator_params()
+        else:
+            disc_params, _ = self.get_param_groups(self.trainable_disc_params, self.disc_optimizer_args)
+        opt_ae = self.instantiate_optimizer_from_config(ae_params, default(self.lr_g_factor, 1.0) * self.learning_rate, self.optimizer_config)
+        opts = [opt_ae]
+        sches = [self.instantiate_scheduler_from_config(opt_ae, self.lr_g_scheduler_config)]
+        if len(disc_params) > 0:
+            opt_disc = self.instantiate_optimizer_from_config(disc_params, self.learning_rate, self.optimizer_config)
+            opts.append(opt_disc)
+            sches.append(self.instantiate_scheduler_from_config(opt_disc, self.lr_d_scheduler_config))
+        return opts, sches
+
+    # ---- log_images: every tensor of it comes out of ops.recon_panels ----
+    @staticmethod
+    def _clip(x: torch.Tensor) -> torch.Tensor:
+        """images [B,3,H,W] as one-frame clips (a view)"""
+        return x.unsqueeze(2) if x.dim() == 4 else x
+
+    def _panels(self, x: torch.Tensor, xrec: torch.Tensor):
+        dt = torch.promote_types(x.dtype, xrec.dtype)  # (autocast: a 16-bit reconstruction of an fp32 clip, as torch promotes it)
+        return ops.recon_panels(self._clip(x).to(dt), self._clip(xrec).to(dt), float(self.diff_boost_factor))
+
+    def _frames(self, x: torch.Tensor) -> torch.Tensor:
+        """b c t h w -> (b t) c h w of one tensor, by the same pass"""
+        return ops.recon_panels(self._clip(x), self._clip(x), 0.0)[0]
+
+    def _log_reconstruction(self, x: torch.Tensor, additional_decode_kwargs: dict, log: dict) -> torch.Tensor:
+        """the pass with the weights as they are: fills the engine's own keys of `log` -> the reconstruction paired with x"""
+        _, xrec, _ = self(x, **additional_decode_kwargs)
+        return xrec
+
+    def _paired(self, x: torch.Tensor, additional_decode_kwargs: dict) -> torch.Tensor:
+        return self(x, **additional_decode_kwargs)[1]
+
+    @torch.no_grad()
+    def log_images(self, batch: dict, additional_log_kwargs: Optional[Dict] = None, **kwargs) -> dict:
+        log = dict()
+        x = self.get_input(batch)
+        additional_decode_kwargs = {key: batch[key] for key in self.additional_decode_keys.intersection(batch)}
+        is_video = x.dim() == 5
+        extra: dict = {}
+        xrec = self._log_reconstruction(x, additional_decode_kwargs, extra)
+        log["inputs"], log["reconstructions"], diff, diff_boost = self._panels(x, xrec)
+        log.update(extra)
+        log["diff"], log["diff_boost"] = diff, diff_boost
+        with self.ema_scope():
+            xrec_ema = self._paired(x, additional_decode_kwargs)
+        if is_video:  # (the reference logs the EMA panels of clips only)
+            _, log["reconstructions_ema"], log["diff_ema"], log["diff_boost_ema"] = self._panels(x, xrec_ema)
+        if additional_log_kwargs:
+            additional_decode_kwargs.update(additional_log_kwargs)
+            xrec_add = self._paired(x, additional_decode_kwargs)
+            log_str = "reconstructions-" + "-".join([f"{key}={additional_log_kwargs[key]}" for key in additional_log_kwargs])
+            log[log_str] = self._panels(x, xrec_add)[1]
+        return log
+
+
+class AutoencodingEngineWithLatentConstraint(AutoencodingEngine):
+    def __init__(
+        self,
+        *args,
+        encoder_config: Dict,
+        decoder_config: Dict,
+        constraint_decoder_config: Dict,
+        loss_config: Dict,
+        regularizer_config: Dict,
+        optimizer_config: Optional[Dict] = None,
+        lr_g_factor: float = 1,
+        lr_g_scheduler_config: Optional[Dict] = None,
+        lr_d_scheduler_config: Optional[Dict] = None,
+        trainable_ae_params: Optional[List[List[str]]] = None,
+        ae_optimizer_args: Optional[List[Dict]] = None,
+        trainable_disc_params: Optional[List[List[str]]] = None,
+        disc_optimizer_args: Optional[List[Dict]] = None,
+        disc_start_iter: int = 0,
+        diff_boost_factor: float = 3,
+        ckpt_engine: Union[None, str, Dict] = None,
+        ckpt_path: Optional[str] = None,
+        additional_decode_keys: Optional[List[str]] = None,
+        trainable: Union[bool, str] = True,
+        **kwargs,
+    ):
+        super().__init__(
+            *args, encoder_config=encoder_config, decoder_config=decoder_config, loss_config=loss_config,
+            regularizer_config=regularizer_config, optimizer_config=optimizer_config, lr_g_factor=lr_g_factor,
+            lr_g_scheduler_config=lr_g_scheduler_config, lr_d_scheduler_config=lr_d_scheduler_config,
+            trainable_ae_params=trainable_ae_params, ae_optimizer_args=ae_optimizer_args, trainable_disc_params=trainable_disc_params,
+            disc_optimizer_args=disc_optimizer_args, disc_start_iter=disc_start_iter, diff_boost_factor=diff_boost_factor,
+            ckpt_engine=None, ckpt_path=None, additional_decode_keys=additional_decode_keys, trainable=trainable, **kwargs)
+        self.constraint_decoder = instantiate_from_config(constraint_decoder_config)
+        self.constraint_decoder.requires_grad_(False)
+        if ckpt_path is not None:
+            assert ckpt_engine is None, "Can't set ckpt_engine and ckpt_path"
+            warnings.warn("Checkpoint path is deprecated, use `ckpt_engine` instead")
+        self.apply_ckpt(default(ckpt_path, ckpt_engine))
+
+    def _networks(self, x: torch.Tensor, **additional_decode_kwargs):
+        z, xrec, regularization_log = self(x, **additional_decode_kwargs)
+        xrec_2d = self.constraint_decoder(z, **additional_decode_kwargs)
+        return z, (xrec, xrec_2d), regularization_log
+
+    def _log_reconstruction(self, x, additional_decode_kwargs, log):
+        z, xrec, _ = self(x, **additional_decode_kwargs)
+        log["reconstructions_2d"] = self._frames(self.constraint_decoder(z, **additional_decode_kwargs))
+        return xrec
+
+
+class AutoencodingEngineWithAllConstraint(AutoencodingEngine):
+    def __init__(
+        self,
+        *args,
+        encoder_config: Dict,
+        decoder_config: Dict,
+        constraint_encoder_config: Dict,
+        constraint_decoder_config: Dict,
+        loss_config: Dict,
+        regularizer_config: Dict,
+        optimizer_config: Optional[Dict] = None,
+        lr_g_factor: float = 1,
+        lr_g_scheduler_config: Optional[Dict] = None,
+        lr_d_scheduler_config: Optional[Dict] = None,
+        trainable_ae_params: Optional[List[List[str]]] = None,
+        ae_optimizer_args: Optional[List[Dict]] = None,
+        trainable_disc_params: Optional[List[List[str]]] = None,
+        disc_optimizer_args: Optional[List[Dict]] = None,
+        disc_start_iter: int = 0,
+        diff_boost_factor: float = 3,
+        ckpt_engine: Union[None, str, Dict] = None,
+        ckpt_path: Optional[str] = None,
+        additional_decode_keys: Optional[List[str]] = None,
+        trainable: Union[bool, str] = True,
+        time_n_compress: Optional[int] = None,
+        **kwargs,
+    ):
+        super().__init__(
+            *args, encoder_config=encoder_config, decoder_config=decoder_config, loss_config=loss_config,
+            regularizer_config=regularizer_config, optimizer_config=optimizer_config, lr_g_factor=lr_g_factor,
+            lr_g_scheduler_config=lr_g_scheduler_config, lr_d_scheduler_config=lr_d_scheduler_config,
+            trainable_ae_params=trainable_ae_params, ae_optimizer_args=ae_optimizer_args, trainable_disc_params=trainable_disc_params,
+            disc_optimizer_args=disc_optimizer_args, disc_start_iter=disc_start_iter, diff_boost_factor=diff_boost_factor,
+            ckpt_engine=None, ckpt_path=None, additional_decode_keys=additional_decode_keys, trainable=trainable, **kwargs)
+        self.constraint_encoder = instantiate_from_config(constraint_encoder_config)
+        self.constraint_encoder.requires_grad_(False)
+        self.constraint_decoder = instantiate_from_config(constraint_decoder_config)
+        self.constraint_decoder.requires_grad_(False)
+        if ckpt_path is not None:
+            assert ckpt_engine is None, "Can't set ckpt_engine and ckpt_path"
+            warnings.warn("Checkpoint path is deprecated, use `ckpt_engine` instead")
+        self.apply_ckpt(default(ckpt_path, ckpt_engine))
+        self.time_n_compress = time_n_compress
+
+    def forward(self, x: torch.Tensor, **additional_decode_kwargs):
+        x_d = x[:, :, :: self.time_n_compress, :, :]
+        with torch.no_grad():
+            z_d = self.constraint_encoder(x_d)
+        z = self.encoder(x)
+        z = torch.cat([z, z_d], dim=0)
+        z, reg_log = self._regularize(z)
+        dec = self.decoder(z, **additional_decode_kwargs)
+        x_d = self.constraint_decoder(z[: z.shape[0] // 2], **additional_decode_kwargs)
+        return z, dec, reg_log, x_d
+
+    def _networks(self, x: torch.Tensor, **additional_decode_kwargs):
+        z, xrec, regularization_log, xrec_2d = self(x, **additional_decode_kwargs)
+        return z, (xrec, xrec_2d), regularization_log
+
+    def _first_reconstruction(self, recs: tuple) -> torch.Tensor:
+        return torch.chunk(recs[0], 2)[0]
+
+    def _log_reconstruction(self, x, additional_decode_kwargs, log):
+        xrec, xrec_d = torch.chunk(self(x, **additional_decode_kwargs)[1], 2)
+        log["rec_d"] = self._panels(x, xrec_d)[1]
+        return xrec
+
+    def _paired(self, x, additional_decode_kwargs):
+        return torch.chunk(self(x, **additional_decode_kwargs)[1], 2)[0]
+
+
+def build_from_config(cfg: Dict) -> AbstractAutoencoder:
+    """cfg: the training YAML as a mapping (`yaml.safe_load`): instantiates cfg["model"] and sets `learning_rate` to its
+    `base_learning_rate`, which is what the reference's main.py does without scaling by batch size and device count"""
+    model_cfg = cfg["model"]
+    engine = instantiate_from_config(model_cfg)
+    if "base_learning_rate" in model_cfg:
+        engine.learning_rate = float(model_cfg["base_learning_rate"])
+    return engine

@@ -30,8 +30,10 @@ frozen 2-D decoder.  It takes all three `target_type`s: "mean" and "random" targ
 autograd node over cvvae_reduce_sum_frames / _bwd, reads "frame index[t']" or "the mean of frames 1+n(t'-1) .. n t'" from the clip
 in place, in the summation order of `reduce` over the materialised target (the same bits).
 
-Not built: `log_images`, `scale_input_to_tgt_size=True`, `target_type` "mean" / "random" on the DomainConstraint class (it keeps
-refusing them at construction; the AllConstraint class has them), per-element `weights`, the AndEncoderConstraint variant.
+`LPIPSWithDiscriminatorAndDomainConstraint(..., frame_maps=True)` takes "mean" / "random" through the same frame maps (one shared
+mixin, `_FrameMapTargets`); without the keyword the class keeps refusing them at construction, as it always did.
+
+Not built: `log_images`, `scale_input_to_tgt_size=True`, per-element `weights`, the AndEncoderConstraint variant.
 """
 import importlib
 from typing import Dict, Iterator, List, Optional, Tuple, Union
@@ -383,7 +385,53 @@ class GeneralLPIPSWithDiscriminator(nn.Module):
         raise NotImplementedError(f"Unknown optimizer_idx {optimizer_idx}")
 
 
-class LPIPSWithDiscriminatorAndDomainConstraint(GeneralLPIPSWithDiscriminator):
+class _FrameMapTargets:
+    """the 2-D term's targets of the two constraint losses: "slice" is the strided view read in place, "mean" and "random" are frame
+    maps of cvvae_reduce_sum_frames (no materialised target).  The random frames are drawn on the CPU with the reference's own
+    expression, so a seeded global generator reproduces its draw; `generator=` seeds the draw, `frame_indices=` replaces it."""
+
+    def draw_frame_indices(self, t: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """target_type "random": frame 0, then one frame of every group of time_n_compress (discriminator_loss.py:855-862)"""
+        d = (t - 1) // self.time_n_compress
+        indices = torch.cat(
+            [
+                torch.tensor([0]),
+                torch.randint(1, self.time_n_compress + 1, (d,), generator=generator)
+                + torch.arange(d) * self.time_n_compress,
+            ]
+        )
+        return indices
+
+    def _rec2d_sum(self, inputs: torch.Tensor, recs2d: torch.Tensor, generator, frame_indices) -> Tuple[torch.Tensor, int, int]:
+        """-> (sum of the 2-D term's rec_loss against the target frames of `inputs`, frames N2, elements), nothing materialised"""
+        b, c, t, h, w = inputs.shape
+        n = self.time_n_compress
+        op = L.RED_ABS_DIFF if self.rec_loss == "l1" else L.RED_SQ_DIFF
+        if self.target_type == "mean" and (t - 1) % n:
+            raise ValueError(f'target_type="mean": the {t - 1} frames behind the first do not split into groups of {n}')
+        if self.target_type == "random":
+            if frame_indices is None:
+                frame_indices = self.draw_frame_indices(t, generator)
+            index = [int(i) for i in (frame_indices.tolist() if isinstance(frame_indices, torch.Tensor) else frame_indices)]
+            if len(index) != 1 + (t - 1) // n or any(i < 0 or i >= t for i in index):
+                raise ValueError(f"frame_indices: {1 + (t - 1) // n} frame numbers in [0, {t}); got {index}")
+            frames2d = len(index)
+        else:
+            frames2d = 1 + (t - 1) // n if self.target_type == "mean" else len(range(0, t, n))
+        want = (b, c, frames2d, h, w)
+        if tuple(recs2d.shape) != want:
+            raise ValueError(f'dims={self.dims}: reconstructions_2d must be {want} (target_type="{self.target_type}", time_n_compress='
+                             f"{n}, inputs {tuple(inputs.shape)}); got {tuple(recs2d.shape)}")
+        if self.target_type == "slice":
+            total = reduce(op, recs2d, inputs[:, :, ::n, :, :])
+        elif self.target_type == "mean":
+            total = reduce_frames(op, recs2d, inputs, L.FMAP_GROUP_MEAN, group=n)
+        else:
+            total = reduce_frames(op, recs2d, inputs, L.FMAP_GATHER, index=index)
+        return total, b * frames2d, recs2d.numel()
+
+
+class LPIPSWithDiscriminatorAndDomainConstraint(_FrameMapTargets, GeneralLPIPSWithDiscriminator):
     def __init__(
         self,
         disc_start: int,
@@ -406,6 +454,7 @@ class LPIPSWithDiscriminatorAndDomainConstraint(GeneralLPIPSWithDiscriminator):
         target_type: str = "slice",
         *,
         discriminator: Optional[nn.Module] = None,
+        frame_maps: bool = False,
     ):
         super().__init__(disc_start, logvar_init, disc_num_layers, disc_in_channels, disc_factor, disc_weight, perceptual_weight,
                          disc_loss, rec_loss, scale_input_to_tgt_size, dims, learn_logvar, regularization_weights,
@@ -414,10 +463,12 @@ class LPIPSWithDiscriminatorAndDomainConstraint(GeneralLPIPSWithDiscriminator):
         self.logvar_2d = nn.Parameter(torch.full((), logvar_init), requires_grad=learn_logvar)
         self.rec2d_weight = rec2d_weight
         assert target_type in ["random", "slice", "mean"]
-        if target_type != "slice":
-            raise NotImplementedError(f'target_type="{target_type}" is not supported: only "slice" (every time_n_compress-th frame, '
-                                      "read in place as a strided view)")
+        if target_type != "slice" and not frame_maps:
+            raise NotImplementedError(f'target_type="{target_type}" is not supported without frame_maps=True: by default only "slice" '
+                                      "(every time_n_compress-th frame, read in place as a strided view); frame_maps=True reads the "
+                                      '"mean" and "random" targets through cvvae_reduce_sum_frames')
         self.target_type = target_type
+        self.frame_maps = bool(frame_maps)
 
     def get_trainable_autoencoder_parameters(self) -> Iterator[nn.Parameter]:
         if self.learn_logvar:
@@ -437,14 +488,26 @@ class LPIPSWithDiscriminatorAndDomainConstraint(GeneralLPIPSWithDiscriminator):
         last_layer: torch.Tensor,
         split: str = "train",
         weights: Union[None, float, torch.Tensor] = None,
+        generator: Optional[torch.Generator] = None,
+        frame_indices=None,
     ) -> Tuple[torch.Tensor, dict]:
         assert self.dims > 2
         self._check_clips(inputs, reconstructions)
-        targets_2d = inputs[:, :, :: self.time_n_compress, :, :]
-        self._check_clips(targets_2d, reconstructions_2d, "reconstructions_2d (against inputs[:, :, ::time_n_compress])")
+        if self.frame_maps:
+            ops._need_gpu(reconstructions_2d)
+            if reconstructions_2d.dim() != 5:
+                raise ValueError(f"dims={self.dims}: reconstructions_2d must be a 5-D tensor; got {tuple(reconstructions_2d.shape)}")
+        else:
+            if generator is not None or frame_indices is not None:
+                raise ValueError("generator= / frame_indices= seed the frame maps: construct the loss with frame_maps=True")
+            targets_2d = inputs[:, :, :: self.time_n_compress, :, :]
+            self._check_clips(targets_2d, reconstructions_2d, "reconstructions_2d (against inputs[:, :, ::time_n_compress])")
         if optimizer_idx == 0:
             rec_sum, n, count = self._rec_sum(inputs, reconstructions, perceptual=True)
-            rec2d_sum, n2, count2 = self._rec_sum(targets_2d, reconstructions_2d, perceptual=False)
+            if self.frame_maps:
+                rec2d_sum, n2, count2 = self._rec2d_sum(inputs, reconstructions_2d, generator, frame_indices)
+            else:
+                rec2d_sum, n2, count2 = self._rec_sum(targets_2d, reconstructions_2d, perceptual=False)
             rec2d_loss = self._nll(rec2d_sum, self.logvar_2d, n2, count2)
             nll_loss = self._nll(rec_sum, self.logvar, n, count)
             weighted_nll_loss = self._weighted(nll_loss, weights) + self.rec2d_weight * rec2d_loss
@@ -468,7 +531,7 @@ class LPIPSWithDiscriminatorAndDomainConstraint(GeneralLPIPSWithDiscriminator):
         raise NotImplementedError(f"Unknown optimizer_idx {optimizer_idx}")
 
 
-class LPIPSWithDiscriminatorAndAllConstraint(GeneralLPIPSWithDiscriminator):
+class LPIPSWithDiscriminatorAndAllConstraint(_FrameMapTargets, GeneralLPIPSWithDiscriminator):
     """discriminator_loss.py:768-1013, the loss of AutoencodingEngineWithAllConstraint (a frozen 2-D encoder AND a frozen 2-D decoder):
     `reconstructions` [2B,3,T,H,W] holds the decodings of the 3-D encoder's latents and then of the frozen 2-D encoder's, `inputs`
     [B,3,T,H,W] stands for cat([inputs, inputs]) -- the pixel sum reads it through a stride-0 outer dimension, LPIPS and the
@@ -514,46 +577,6 @@ class LPIPSWithDiscriminatorAndAllConstraint(GeneralLPIPSWithDiscriminator):
             for param in [self.logvar, self.logvar_2d]:
                 yield param
         yield from ()
-
-    def draw_frame_indices(self, t: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
-        """target_type "random": frame 0, then one frame of every group of time_n_compress (discriminator_loss.py:855-862)"""
-        d = (t - 1) // self.time_n_compress
-        indices = torch.cat(
-            [
-                torch.tensor([0]),
-                torch.randint(1, self.time_n_compress + 1, (d,), generator=generator)
-                + torch.arange(d) * self.time_n_compress,
-            ]
-        )
-        return indices
-
-    def _rec2d_sum(self, inputs: torch.Tensor, recs2d: torch.Tensor, generator, frame_indices) -> Tuple[torch.Tensor, int, int]:
-        """-> (sum of the 2-D term's rec_loss against the target frames of `inputs`, frames N2, elements), nothing materialised"""
-        b, c, t, h, w = inputs.shape
-        n = self.time_n_compress
-        op = L.RED_ABS_DIFF if self.rec_loss == "l1" else L.RED_SQ_DIFF
-        if self.target_type == "mean" and (t - 1) % n:
-            raise ValueError(f'target_type="mean": the {t - 1} frames behind the first do not split into groups of {n}')
-        if self.target_type == "random":
-            if frame_indices is None:
-                frame_indices = self.draw_frame_indices(t, generator)
-            index = [int(i) for i in (frame_indices.tolist() if isinstance(frame_indices, torch.Tensor) else frame_indices)]
-            if len(index) != 1 + (t - 1) // n or any(i < 0 or i >= t for i in index):
-                raise ValueError(f"frame_indices: {1 + (t - 1) // n} frame numbers in [0, {t}); got {index}")
-            frames2d = len(index)
-        else:
-            frames2d = 1 + (t - 1) // n if self.target_type == "mean" else len(range(0, t, n))
-        want = (b, c, frames2d, h, w)
-        if tuple(recs2d.shape) != want:
-            raise ValueError(f'dims={self.dims}: reconstructions_2d must be {want} (target_type="{self.target_type}", time_n_compress='
-                             f"{n}, inputs {tuple(inputs.shape)}); got {tuple(recs2d.shape)}")
-        if self.target_type == "slice":
-            total = reduce(op, recs2d, inputs[:, :, ::n, :, :])
-        elif self.target_type == "mean":
-            total = reduce_frames(op, recs2d, inputs, L.FMAP_GROUP_MEAN, group=n)
-        else:
-            total = reduce_frames(op, recs2d, inputs, L.FMAP_GATHER, index=index)
-        return total, b * frames2d, recs2d.numel()
 
     def forward(
         self,

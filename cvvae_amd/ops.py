@@ -979,6 +979,42 @@ def frame_metrics(a: torch.Tensor, b: torch.Tensor, quantize: bool = True, want_
     return sse, psnr, ssim
 
 
+# ---- the panels of log_images (include/cvvae.h cvvae_recon_panels; cvvae_amd/autoencoder.py) ----
+def check_panel_operands(x: torch.Tensor, xrec: torch.Tensor) -> Tuple[int, int, int, int]:
+    """the ValueErrors of recon_panels, raised before anything touches the device -> (B, T, H, W)"""
+    for t in (x, xrec):
+        if t.dtype not in _DT:
+            raise ValueError(f"recon_panels: operands are fp16 / bf16 / fp32 clips; got {t.dtype}")
+        if t.dim() != 5 or t.shape[1] != 3:
+            raise ValueError(f"recon_panels: clips are [B,3,T,H,W]; got {tuple(t.shape)}")
+    if x.dtype != xrec.dtype:
+        raise ValueError(f"recon_panels: operands of one dtype; got {x.dtype} and {xrec.dtype}")
+    if x.shape != xrec.shape:
+        raise ValueError(f"recon_panels: operands of shapes {tuple(x.shape)} and {tuple(xrec.shape)}")
+    if x.device != xrec.device:
+        raise ValueError(f"recon_panels: operands on {x.device} and {xrec.device}")
+    if x.numel() == 0:
+        raise ValueError(f"recon_panels: empty operand {tuple(x.shape)}")
+    return (x.shape[0],) + tuple(x.shape[2:])
+
+
+def recon_panels(x: torch.Tensor, xrec: torch.Tensor, boost: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """x, xrec: [B,3,T,H,W] clips of one dtype (views with a unit innermost stride are read in place) -> (inputs, reconstructions,
+    diff, diff_boost), contiguous [(B T),3,H,W] in that dtype: the four panels of the engines' log_images,
+    diff = 2 clamp(0.5 |clamp(xrec,-1,1) - x|, 0, 1) - 1 and diff_boost with `boost` inside the outer clamp, bit for bit the eager
+    expression in that dtype.  One launch, no host sync."""
+    lib = L.load()
+    _need_gpu(x)
+    _need_gpu(xrec)
+    B, T, H, W = check_panel_operands(x, xrec)
+    x, vx = _clip_view(x)
+    xrec, vr = _clip_view(xrec)
+    outs = tuple(torch.empty((B * T, 3, H, W), dtype=x.dtype, device=x.device) for _ in range(4))
+    L.check(lib.cvvae_recon_panels(x.data_ptr(), ctypes.byref(vx), xrec.data_ptr(), ctypes.byref(vr), B, T, H, W, float(boost),
+                                   *[o.data_ptr() for o in outs], _stream(x)), "cvvae_recon_panels")
+    return outs
+
+
 # ---- the passes around the VGG16 convolutions of the LPIPS perceptual loss (include/cvvae.h ABI 14; cvvae_amd/lpips.py) ----
 def lpips_scale_in(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, cpad: int, dtype: torch.dtype,
                    out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -709,6 +709,28 @@ int cvvae_frame_metrics(const void* a, const cvvae_clip_view* va, const void* b,
                         int32_t H, int32_t W, int32_t quantize, int32_t want_ssim, double* sse, float* psnr, float* ssim,
                         void* workspace, void* stream);
 
+/*
+ * The panels of the training engines' log_images (cvvae_amd/autoencoder.py; csrc/panel_kernels.hip) as one pass.  An addition to
+ * ABI 14: no existing entry point or struct changed, so the version number stays.
+ *
+ * x and xrec are float clips [B][3][T][H][W] of one dtype (CVVAE_CLIP_NCTHW; CVVAE_F16 / BF16 / F32; strides in elements, a row is W
+ * contiguous elements), read in place and once each.  The four outputs are contiguous [(B T)][3][H][W] tensors of that dtype:
+ *   inputs = x;   reconstructions = xrec (unclamped);
+ *   diff       = 2 * clamp(    0.5 * |clamp(xrec,-1,1) - x|, 0, 1) - 1;
+ *   diff_boost = 2 * clamp(f * 0.5 * |clamp(xrec,-1,1) - x|, 0, 1) - 1.
+ * Every operation is rounded to the dtype where eager torch rounds it (the subtraction, 0.5 *, f *, 2 *, - 1); f multiplies in fp32.
+ * The results are bit for bit those of the expression evaluated by torch on tensors of that dtype.  NaN is outside the contract.
+ * One launch, sized from the element count; 16-byte loads and stores where a row's address and width allow, element by element at
+ * the head and tail of a row otherwise.
+ *
+ * Before any launch.  CVVAE_EINVAL: a NULL x, xrec, view or output, a pointer not aligned to its element, a non-positive extent, a
+ * negative stride, sy smaller than a row.  CVVAE_EUNSUPPORTED: a layout other than CVVAE_CLIP_NCTHW, an unknown dtype, two dtypes,
+ * H, W or B * T > 2^20.
+ */
+int cvvae_recon_panels(const void* x, const cvvae_clip_view* vx, const void* xrec, const cvvae_clip_view* vr, int32_t B, int32_t T,
+                       int32_t H, int32_t W, float boost, void* inputs, void* reconstructions, void* diff, void* diff_boost,
+                       void* stream);
+
 int cvvae_abi_version(void);
 /* name of the kernel instance cvvae_conv_fwd would launch for d (for profiling reports); NULL if unsupported */
 const char* cvvae_conv_kernel_name(const cvvae_conv_desc* d);
