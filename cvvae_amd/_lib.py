@@ -175,16 +175,18 @@ PROTOTYPES = {
                                    _vp, _vp, _vp, _vp, _vp]),
     "cvvae_recon_panels": (_i32, [_vp, ctypes.POINTER(ClipView), _vp, ctypes.POINTER(ClipView), _i32, _i32, _i32, _i32, _f32,
                                   _vp, _vp, _vp, _vp, _vp]),
+    "cvvae_clip_from_frames_u8": (_i32, [_vp, ctypes.POINTER(ClipView), _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32,
+                                         _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, ctypes.POINTER(ClipView), _vp]),
 }
 
 _lib = None
 
 
 # translation units whose kernels only run in training (weight gradients, channel sums, their reductions) or in scoring a
-# reconstruction (metrics_kernels.hip) or in logging one (panel_kernels.hip): no launch of an
+# reconstruction (metrics_kernels.hip), in logging one (panel_kernels.hip) or in making a batch (clip_kernels.hip): no launch of an
 # encode / decode step comes from them, so the counters of the inference bench do not go stale when they change
 TRAINING_ONLY_SOURCES = ("wgrad_kernel.hip", "loss_kernels.hip", "disc_kernels.hip", "optim_kernels.hip", "metrics_kernels.hip",
-                         "panel_kernels.hip")
+                         "panel_kernels.hip", "clip_kernels.hip")
 
 
 def source_fingerprint() -> str:

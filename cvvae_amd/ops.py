@@ -1015,6 +1015,84 @@ def recon_panels(x: torch.Tensor, xrec: torch.Tensor, boost: float) -> Tuple[tor
     return outs
 
 
+# ---- the training clip transform (include/cvvae.h cvvae_clip_from_frames_u8; cvvae_amd/data.py) ----
+@dataclass
+class ClipAxisTable:
+    """the tap tables of one axis of clip_from_frames_u8 for the crop window's n output positions: position i is
+    sum_j w[i, j] * src[amin[i] + j] over j < asize[i].  amin / asize: int32 [n], w: fp32 [n, k], all contiguous on the frames'
+    device; [lo, hi) is the span of input positions they touch, known on the host (cvvae_amd/data.py builds these)."""
+    amin: torch.Tensor
+    asize: torch.Tensor
+    w: torch.Tensor
+    k: int
+    lo: int
+    hi: int
+
+    @property
+    def n(self) -> int:
+        return int(self.amin.shape[0])
+
+
+def check_clip_operands(frames: torch.Tensor, frame_index: Optional[torch.Tensor], ytab: ClipAxisTable, xtab: ClipAxisTable,
+                        out_slot: torch.Tensor) -> Tuple[int, int, int, int]:
+    """the ValueErrors of clip_from_frames_u8, raised before anything touches the device -> (T_in, H, W, T_out)"""
+    if frames.dtype != torch.uint8:
+        raise ValueError(f"clip_from_frames_u8: frames are uint8; got {frames.dtype}")
+    if frames.dim() != 4 or frames.shape[-1] != 3 or frames.numel() == 0:
+        raise ValueError(f"clip_from_frames_u8: frames are [T,H,W,3], not empty; got {tuple(frames.shape)}")
+    if not frames.is_cuda:
+        raise ValueError(f"clip_from_frames_u8: frames on {frames.device}; the pass runs on the GPU (cvvae_amd.data.ClipTransform uploads)")
+    T_in, H, W, _ = frames.shape
+    T_out = T_in
+    if frame_index is not None:
+        if frame_index.dtype != torch.int32 or frame_index.dim() != 1 or frame_index.numel() == 0 or not frame_index.is_contiguous():
+            raise ValueError(f"clip_from_frames_u8: frame_index is a contiguous int32 [T_out]; got {frame_index.dtype} "
+                             f"{tuple(frame_index.shape)}")
+        if frame_index.device != frames.device:
+            raise ValueError(f"clip_from_frames_u8: frame_index on {frame_index.device}, frames on {frames.device}")
+        T_out = int(frame_index.numel())
+    for name, tab, n_in in (("ytab", ytab, H), ("xtab", xtab, W)):
+        n = tab.n
+        if (tab.amin.dtype != torch.int32 or tab.asize.dtype != torch.int32 or tab.w.dtype != torch.float32 or tab.k < 1 or n < 1
+                or tuple(tab.amin.shape) != (n,) or tuple(tab.asize.shape) != (n,) or tuple(tab.w.shape) != (n, tab.k)
+                or not (tab.amin.is_contiguous() and tab.asize.is_contiguous() and tab.w.is_contiguous())):
+            raise ValueError(f"clip_from_frames_u8: {name} is int32 [n], int32 [n], fp32 [n,k] (contiguous, n >= 1, k >= 1)")
+        if any(t.device != frames.device for t in (tab.amin, tab.asize, tab.w)):
+            raise ValueError(f"clip_from_frames_u8: {name} is not on the frames' device {frames.device}")
+        if not 0 <= tab.lo < tab.hi <= n_in:
+            raise ValueError(f"clip_from_frames_u8: {name} touches [{tab.lo},{tab.hi}) of {n_in} input positions")
+    if out_slot.dtype not in _DT:
+        raise ValueError(f"clip_from_frames_u8: the slot is fp16 / bf16 / fp32; got {out_slot.dtype}")
+    if tuple(out_slot.shape) != (3, T_out, ytab.n, xtab.n):
+        raise ValueError(f"clip_from_frames_u8: the slot is [3,{T_out},{ytab.n},{xtab.n}]; got {tuple(out_slot.shape)}")
+    if out_slot.device != frames.device:
+        raise ValueError(f"clip_from_frames_u8: the slot on {out_slot.device}, frames on {frames.device}")
+    if out_slot.stride(3) != 1 or out_slot.stride(2) < xtab.n or min(out_slot.stride()) < 0:
+        raise ValueError(f"clip_from_frames_u8: the slot's rows are contiguous (it is written in place); strides {out_slot.stride()}")
+    return T_in, H, W, T_out
+
+
+def clip_from_frames_u8(frames: torch.Tensor, frame_index: Optional[torch.Tensor], ytab: ClipAxisTable, xtab: ClipAxisTable,
+                        out_slot: torch.Tensor) -> torch.Tensor:
+    """uint8 frames [T_in,H,W,3] on the device -> out_slot [3,T_out,oh,ow] (a view such as batch[b], written in place) =
+    ((resampled crop window / 255) - 0.5) * 2: frame selection, the float resize of only the window the tables describe, the
+    normalisation and the layout move in ONE launch.  frame_index: int32 device table [T_out] or None (frames 0..T_in-1).  fp32 FMA
+    chains in tap order, one rounding to the slot's dtype.  No host sync."""
+    T_in, H, W, T_out = check_clip_operands(frames, frame_index, ytab, xtab, out_slot)
+    lib = L.load()
+    frames, vin = _clip_view(frames)
+    vout = L.ClipView()
+    vout.layout, vout.dtype = L.CLIP_NCTHW, _DT[out_slot.dtype]
+    vout.sb, (vout.sc, vout.st, vout.sy, _) = 0, out_slot.stride()
+    L.check(lib.cvvae_clip_from_frames_u8(frames.data_ptr(), ctypes.byref(vin), T_in, H, W,
+                                          None if frame_index is None else frame_index.data_ptr(), T_out,
+                                          ytab.amin.data_ptr(), ytab.asize.data_ptr(), ytab.w.data_ptr(), ytab.k, ytab.n,
+                                          xtab.amin.data_ptr(), xtab.asize.data_ptr(), xtab.w.data_ptr(), xtab.k, xtab.n,
+                                          ytab.lo, ytab.hi, xtab.lo, xtab.hi, out_slot.data_ptr(), ctypes.byref(vout),
+                                          _stream(frames)), "cvvae_clip_from_frames_u8")
+    return out_slot
+
+
 # ---- the passes around the VGG16 convolutions of the LPIPS perceptual loss (include/cvvae.h ABI 14; cvvae_amd/lpips.py) ----
 def lpips_scale_in(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, cpad: int, dtype: torch.dtype,
                    out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -731,6 +731,37 @@ int cvvae_recon_panels(const void* x, const cvvae_clip_view* vx, const void* xre
                        int32_t H, int32_t W, float boost, void* inputs, void* reconstructions, void* diff, void* diff_boost,
                        void* stream);
 
+/*
+ * The training data side's per-sample transform as one pass (cvvae_amd/data.py; csrc/clip_kernels.hip): decoded uint8 frames -> one
+ * slot of the training batch.  An addition to ABI 14: no existing entry point or struct changed, so the version number stays.
+ *
+ * frames: uint8 [T_in][H][W][3] (vin: CVVAE_CLIP_THWC_U8; st, sy in bytes, a row is 3W contiguous bytes, no alignment asked).
+ * out: the slot [3][T_out][oh][ow] of a batch (vout: CVVAE_CLIP_NCTHW; dtype CVVAE_F16 / BF16 / F32; sc, st, sy in elements, a row is ow
+ * contiguous elements; sb is not read: the caller passes the slot's base pointer).  Output frame t is made from input frame
+ * frame_index[t] (a device table of T_out entries in [0, T_in)), or from frame t when frame_index is NULL (then T_out <= T_in).
+ *
+ * The tables are device memory built by the caller and describe ONLY the crop window: entry i of the y tables is output row i,
+ *   row i = sum over j < ysize[i] of yw[i * kh + j] * src[ymin[i] + j],   1 <= ysize[i] <= kh,
+ * and x alike with xmin, xsize, xw, kw.  The kernel trusts their values (the precedent of cvvae_mt_*); [y_lo, y_hi) and [x_lo, x_hi)
+ * are the host-known spans of input rows and columns the tables touch, so that tables that would leave the frame are refused here.
+ *
+ * Value, per channel: the horizontal pass, then the vertical pass over its fp32 results; each pass is acc = w0 * s0 followed by
+ * acc = fma(wj, sj, acc) in tap order, fp32; then ((acc / 255) - 0.5) * 2 in fp32 with an IEEE division, and ONE rounding to the output
+ * dtype.  Nothing is atomic and every output element has one writer; its bits are a function of the frame's bytes and the table
+ * entries alone, wherever it falls in a workgroup's tile.  One launch: a workgroup per frame, R output rows and 64 output columns
+ * stages the horizontally resampled input rows in LDS (at most 64 rows = 48 KiB; R from {16, 8, 4, 2, 1} so that they fit).
+ *
+ * Before any launch.  CVVAE_EINVAL: a NULL pointer other than frame_index, a non-positive extent, kh or kw < 1, a negative stride,
+ * vin->sy < 3W or vout->sy < ow, out not aligned to its element, a span that is empty or outside [0, H) / [0, W).  CVVAE_EUNSUPPORTED:
+ * vin not CVVAE_CLIP_THWC_U8, vout not CVVAE_CLIP_NCTHW, an unknown dtype, H, W, oh or ow > 2^20, T_out > 65535, kh > 64 (one output
+ * row's taps do not fit the stage: an antialiased downscale beyond about 31x).
+ */
+int cvvae_clip_from_frames_u8(const uint8_t* frames, const cvvae_clip_view* vin, int32_t T_in, int32_t H, int32_t W,
+                              const int32_t* frame_index, int32_t T_out, const int32_t* ymin, const int32_t* ysize, const float* yw,
+                              int32_t kh, int32_t oh, const int32_t* xmin, const int32_t* xsize, const float* xw, int32_t kw, int32_t ow,
+                              int32_t y_lo, int32_t y_hi, int32_t x_lo, int32_t x_hi, void* out, const cvvae_clip_view* vout,
+                              void* stream);
+
 int cvvae_abi_version(void);
 /* name of the kernel instance cvvae_conv_fwd would launch for d (for profiling reports); NULL if unsupported */
 const char* cvvae_conv_kernel_name(const cvvae_conv_desc* d);
