@@ -38,7 +38,10 @@ applied the `trainable` switch, under the same name and with the same buffer nam
 over the two clips per call, under `torch.no_grad()`.
 
 Not built: AutoencodingEngineWithEncoderConstraint (its loss in the reference reads `self.logvar_2d`, which that class never
-creates), the legacy / VQ engines of that file, a Lightning adapter, DDP, the data module.
+creates), the legacy / VQ engines of that file, a Lightning adapter, the data module.
+
+Data parallelism (the YAML's `strategy: ddp`) is `engine.data_parallel(group)`: a broadcast of the state from rank 0, then one packed
+gradient all-reduce per iteration between the backward and the clip (cvvae_amd/ddp.py).  Without that call nothing here changes.
 """
 import inspect
 import re
@@ -87,6 +90,52 @@ class AbstractAutoencoder(nn.Module):
         self.validation_meter = None
         self._opts: Optional[list] = None
         self._sches: Optional[list] = None
+        self._dp: Optional[dict] = None     # data_parallel(): the group, GradientSync's keywords and one GradientSync per optimizer
+
+    # ---- data parallelism (cvvae_amd/ddp.py) ----
+    def data_parallel(self, group=None, **sync_kwargs) -> "AbstractAutoencoder":
+        """make this engine one replica of `group` (None: the default process group): every parameter and buffer -- the EMA shadows
+        and `num_updates` among them -- is broadcast from the group's rank 0, one plain broadcast per tensor (once, not hot), and
+        `training_step` from now on exchanges the gradients between `manual_backward` and the clip through one
+        `ddp.GradientSync(params of the optimizer, group, **sync_kwargs)` per optimizer, made on its first use.  `validation_step`
+        then averages its logs over the group.  The train logs stay rank-local, the learning rate is not scaled by the group's size
+        and the sampler is the caller's, as with the reference's `strategy: ddp` without `--scale_lr`.  Call it on every rank,
+        before the first `training_step` (optimizer state is not broadcast)."""
+        from . import ddp
+        written = []
+        for t in list(self.parameters()) + list(self.buffers()):
+            ddp.broadcast(t.detach(), group)
+            written.append(t)
+        if ddp.world_size(group) > 1:
+            torch.autograd.graph.increment_version(written)   # as every other writer of a parameter: the weight caches key on it
+            if self.use_ema:
+                self.model_ema._forget_host()                 # num_updates may have moved: the host mirror is read again
+        self._dp = {"group": group, "kwargs": dict(sync_kwargs), "syncs": {}}
+        return self
+
+    def gradient_sync(self, optimizer):
+        """the GradientSync of `optimizer` under data_parallel() (made on first use), else None"""
+        if self._dp is None:
+            return None
+        sync = self._dp["syncs"].get(id(optimizer))
+        if sync is None:
+            from . import ddp
+            sync = self._dp["syncs"][id(optimizer)] = ddp.GradientSync(
+                [p for g in optimizer.param_groups for p in g["params"]], self._dp["group"], **self._dp["kwargs"])
+        return sync
+
+    def _group_mean(self, logs: Dict[str, Any]) -> Dict[str, Any]:
+        """the 0-dim entries of `logs` averaged over the data-parallel group by ONE all-reduce of the stacked values (the
+        reference's `sync_dist=True`); other entries stay"""
+        from . import ddp
+        keys = [k for k, v in logs.items() if torch.is_tensor(v) and v.dim() == 0]
+        world = ddp.world_size(self._dp["group"])
+        if not keys or world == 1:
+            return logs
+        stacked = ddp.all_reduce_sum(torch.stack([logs[k].detach().float() for k in keys]), self._dp["group"]) / world
+        out = dict(logs)
+        out.update({k: stacked[i].to(logs[k].dtype) for i, k in enumerate(keys)})
+        return out
 
     def _build_ema(self) -> None:
         """(re)build `model_ema` over the parameters that require grad NOW: called by a constructor once its networks exist"""
@@ -360,6 +409,8 @@ class AutoencodingEngine(AbstractAutoencoder):
         with self.toggle_model(opt):
             loss = self.inner_training_step(batch, batch_idx, optimizer_idx=optimizer_idx)
             self.manual_backward(loss)
+            if self._dp is not None:   # the clip's norm must be the norm of the AVERAGED gradients
+                self.gradient_sync(opt).sync()
             self.clip_gradients(opt, gradient_clip_val=1.0, gradient_clip_algorithm="norm")
         opt.step()
         self.global_step += 1
@@ -382,6 +433,9 @@ class AutoencodingEngine(AbstractAutoencoder):
                 log_dict.update(log_dict_ema)
         finally:
             self.train(was_training)
+        if self._dp is not None:
+            log_dict = self._group_mean(log_dict)
+            self.last_logs.update(log_dict)
         return log_dict
 
     def _first_reconstruction(self, recs: tuple) -> torch.Tensor:

@@ -1,6 +1,7 @@
 // optim_kernels.hip -- the parameter update of a training iteration (cvvae_amd/optim.py, lvdm/modules/ema.py) as multi-tensor passes
 // over a LIST of fp32 tensors: the L2 norm of all gradients with the clip coefficient, g <- coef g, AdamW with the coefficient applied
-// in flight, and the EMA of the weights.  gfx950 only.  All of them are HBM-bound: plain C++.
+// in flight, the EMA of the weights, and the pack pass of the data-parallel gradient exchange (cvvae_amd/ddp.py: g / world size into
+// the slots of one flat bucket).  gfx950 only.  All of them are HBM-bound: plain C++.
 //
 // Geometry.  The list is cut into chunks of at most CHUNK elements that never straddle two tensors (cvvae_mt_chunk: tensor index,
 // first element, length); the tensors' base pointers and per-tensor scalars sit in a second table (cvvae_mt_tensor).  One workgroup
@@ -134,6 +135,31 @@ __global__ __launch_bounds__(WG) void ema_kernel(const cvvae_mt_chunk* __restric
   }
 }
 
+// shadow <- g / divisor (zeros for a tensor without a gradient: g NULL).  `/` is the correctly rounded fp32 division (hipcc's default;
+// the Makefile sets no fast-math flag), as in adamw_kernel.  g and shadow carry no __restrict__: they may be one address.
+__global__ __launch_bounds__(WG) void pack_kernel(const cvvae_mt_chunk* __restrict__ chunks, const cvvae_mt_tensor* __restrict__ tensors,
+                                                  long long n_chunks, float divisor) {
+  for (long long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    const cvvae_mt_chunk ch = chunks[c];
+    const cvvae_mt_tensor t = tensors[ch.tensor];
+    const float* g = t.g ? (const float*)t.g + ch.start : nullptr;
+    float* d = (float*)t.shadow + ch.start;
+    for (int i = threadIdx.x * VEC; i < ch.n; i += TILE) {
+      const int n = (ch.n - i) < VEC ? (ch.n - i) : VEC;
+      float f[VEC];
+      if (g) {
+        ld8_n(g + i, n, f);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) f[k] = f[k] / divisor;
+      } else {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) f[k] = 0.f;
+      }
+      st8_n(d + i, f, n);
+    }
+  }
+}
+
 static inline int blocks_for(long long n_chunks) { return (int)(n_chunks < MAX_BLOCKS ? n_chunks : MAX_BLOCKS); }
 
 // CVVAE_OK when the launch has something to do, 1 when the list is empty (nothing to launch), else the error
@@ -198,6 +224,16 @@ int cvvae_mt_ema(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_ten
   if (rc != 0) return rc < 0 ? rc : CVVAE_OK;
   hipLaunchKernelGGL(ema_kernel, dim3(blocks_for(n_chunks)), dim3(WG), 0, (hipStream_t)stream, chunks, tensors, (long long)n_chunks,
                      one_minus_decay);
+  return launch_status();
+}
+
+int cvvae_mt_pack(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float divisor,
+                  void* stream) {
+  if (!(divisor > 0.f) || !(divisor <= 3.402823466e38f)) return CVVAE_EINVAL;
+  const int rc = check_list(dtype, chunks, tensors, n_chunks);
+  if (rc != 0) return rc < 0 ? rc : CVVAE_OK;
+  hipLaunchKernelGGL(pack_kernel, dim3(blocks_for(n_chunks)), dim3(WG), 0, (hipStream_t)stream, chunks, tensors, (long long)n_chunks,
+                     divisor);
   return launch_status();
 }
 

@@ -30,8 +30,9 @@ kernel; parameter gradients are accumulated in fp32 and cast to the parameter's 
 padding, GroupNorm eps and names from the tape, so the vae3d (SD2.1-compatible) family's ENCODER (vae_models.py:790-823: zero H / W
 padding, asymmetric Downsample3D pads, eps 1e-5) trains through it too, and so does its DECODER (vae_models.py:960-1002): the temporal half of MemoryEfficientAttnVideoBlock
 has its own backward kernel (`cvvae_temporal_attention_bwd`), its LayerNorm runs on the GroupNorm kernels (one group, rows = tokens).
-Not built yet: spatial tiling / temporal windows under autograd (one window, one tile per call: the training crops of the
-reference's configs fit one).
+Spatial tiling and temporal windows run under autograd too: the tiled wrapper's blends are `BlendFn` (modeling._blend), and with
+`net.recompute` every (window, tile) unit is one `Net3DRecomputeFn` node.  The training crops of the reference's configs fit one
+window and one tile.
 """
 from typing import Dict, List, Optional, Tuple
 

@@ -71,11 +71,16 @@ class ReconstructionMeter:
         self._acc = add if self._acc is None else self._acc + add
         return m
 
-    def compute(self) -> Dict[str, float]:
+    def compute(self, group=None) -> Dict[str, float]:
         """-> {"psnr": mean over the non-identical frames (nan if there is none), "ssim", "lpips" (None without the network), "frames",
-        "identical_frames"} as plain Python numbers; one device-to-host copy"""
+        "identical_frames"} as plain Python numbers; one device-to-host copy.  group (a torch.distributed process group): the six
+        sums are all-reduced over it first, so every rank returns the figures pooled over all ranks' clips; the meter's own sums stay"""
         if self._acc is None:
             raise RuntimeError("ReconstructionMeter.compute() before any update()")
-        s_psnr, n_finite, n_same, s_ssim, s_lpips, n = self._acc.tolist()
+        acc = self._acc
+        if group is not None:
+            from .ddp import all_reduce_sum
+            acc = all_reduce_sum(acc.clone(), group)
+        s_psnr, n_finite, n_same, s_ssim, s_lpips, n = acc.tolist()
         return {"psnr": s_psnr / n_finite if n_finite else float("nan"), "ssim": s_ssim / n,
                 "lpips": s_lpips / n if self.lpips is not None else None, "frames": int(n), "identical_frames": int(n_same)}

@@ -1557,14 +1557,15 @@ class MultiTensorList:
 
     def set(self, step_size=None, bias2_sqrt=None, **fields) -> "MultiTensorList":
         """fields: g / p / m / v / shadow = a sequence of n_tensors tensors each; step_size / bias2_sqrt: n_tensors floats (cvvae_mt_adamw's
-        per-tensor scalars).  Fields not given keep their last value."""
+        per-tensor scalars).  Fields not given keep their last value.  None in a field's sequence stores a null pointer for that
+        tensor (cvvae_mt_pack: a parameter without a gradient)."""
         import numpy as np
         img = self._image
         for f, ts in fields.items():
             col = MT_FIELDS.index(f)
             if len(ts) != self.n_tensors:
                 raise ValueError(f"MultiTensorList.set: {len(ts)} tensors for field {f!r} of a list of {self.n_tensors}")
-            img[:self.n_tensors, col] = [t.data_ptr() for t in ts]
+            img[:self.n_tensors, col] = [0 if t is None else t.data_ptr() for t in ts]
             self.tensors[f] = ts
         if step_size is not None:
             scal = img.view(np.float32)
@@ -1642,3 +1643,10 @@ def mt_ema(mtl: MultiTensorList, one_minus_decay: float) -> None:
     """shadow <- shadow - one_minus_decay (shadow - p) over the list"""
     lib, dt, chunks, table, n = _mt_args(mtl, ("p", "shadow"))
     L.check(lib.cvvae_mt_ema(dt, chunks, table, n, float(one_minus_decay), _stream(mtl.table)), "cvvae_mt_ema")
+
+
+def mt_pack(mtl: MultiTensorList, divisor: float) -> None:
+    """shadow <- g / divisor over the list (include/cvvae.h cvvae_mt_pack): the gradients into their slots of the bucket that the
+    data-parallel exchange all-reduces (cvvae_amd/ddp.py), zeros where the list's g entry is None.  A correctly rounded fp32 division"""
+    lib, dt, chunks, table, n = _mt_args(mtl, ("g", "shadow"))
+    L.check(lib.cvvae_mt_pack(dt, chunks, table, n, float(divisor), _stream(mtl.table)), "cvvae_mt_pack")

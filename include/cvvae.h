@@ -647,6 +647,12 @@ int cvvae_conv333_s2_dgrad_small(int32_t dtype, const void* gy, int64_t gy_pix_s
  * with the PER-TENSOR step_size = lr / (1 - beta1^t) and bias2_sqrt = sqrt(1 - beta2^t) of its own step count t, computed by the
  * caller in double: tensors at different t share a launch.  The hyper-parameters are doubles, rounded to fp32 once after 1 - x.
  * cvvae_mt_ema (reads p; updates shadow): s <- s - one_minus_decay (s - p).
+ * cvvae_mt_pack (reads g; writes shadow): the pack pass of the data-parallel gradient exchange (cvvae_amd/ddp.py).  The destination
+ * of tensor i is its `shadow` field -- here the tensor's slot of the flat bucket that is all-reduced, the gradient's copy:
+ *   shadow_i[k] = g_i[k] / divisor,   and shadow_i[k] = 0 for a tensor whose g is NULL (no gradient this iteration).
+ * The quotient is the correctly rounded IEEE fp32 division (what DistributedDataParallel applies before its sum), NOT a product with
+ * a reciprocal: the two differ in the last bit for a divisor such as 3.  divisor must be > 0 and finite (else CVVAE_EINVAL).  g and
+ * shadow of a tensor may be the same address (element k is read, then written, by one thread).  An addition to ABI 14.
  */
 #define CVVAE_MT_CHUNK 8192                 /* elements; a multiple of the loss kernels' 2048-element tile */
 #define CVVAE_MT_MAX_CHUNKS (1LL << 31)
@@ -673,6 +679,8 @@ int cvvae_mt_adamw(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_t
                    double beta2, double eps, double weight_decay, const float* coef_dev, void* stream);
 int cvvae_mt_ema(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float one_minus_decay,
                  void* stream);
+int cvvae_mt_pack(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float divisor,
+                  void* stream);
 
 /*
  * Per-frame reconstruction metrics of two clips on the 8-bit scale, data_range = 255 (cvvae_amd/metrics.py; csrc/metrics_kernels.hip):
