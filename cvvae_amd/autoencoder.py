@@ -42,6 +42,10 @@ creates), the legacy / VQ engines of that file, a Lightning adapter, the data mo
 
 Data parallelism (the YAML's `strategy: ddp`) is `engine.data_parallel(group)`: a broadcast of the state from rank 0, then one packed
 gradient all-reduce per iteration between the backward and the clip (cvvae_amd/ddp.py).  Without that call nothing here changes.
+
+16-bit networks that learn are `engine.master_weights()`: bf16 networks on fp32 master weights that the optimizers own
+(cvvae_amd.optim.AdamW(master_weights=True)), the EMA in fp32 over the masters, `master_state_dict()` for the checkpoint.  Without
+that call nothing here changes either: networks cast to bf16 by hand take torch's 16-bit step, which cannot move a weight of size 1.
 """
 import inspect
 import re
@@ -61,6 +65,7 @@ from . import optim as _optim
 __all__ = ["AbstractAutoencoder", "AutoencodingEngine", "AutoencodingEngineWithLatentConstraint",
            "AutoencodingEngineWithAllConstraint", "build_from_config"]
 
+_CAST_TO_16 = ("encoder", "decoder", "constraint_encoder", "constraint_decoder")   # and loss.perceptual_loss, loss.discriminator
 _CONSTANT = {"target": "lvdm.lr_scheduler.get_scheduler", "params": {"name": "constant"}}
 
 
@@ -91,6 +96,7 @@ class AbstractAutoencoder(nn.Module):
         self._opts: Optional[list] = None
         self._sches: Optional[list] = None
         self._dp: Optional[dict] = None     # data_parallel(): the group, GradientSync's keywords and one GradientSync per optimizer
+        self._master: Optional[dict] = None  # master_weights(): the 16-bit dtype and the fp32 seed of every parameter that was cast
 
     # ---- data parallelism (cvvae_amd/ddp.py) ----
     def data_parallel(self, group=None, **sync_kwargs) -> "AbstractAutoencoder":
@@ -98,12 +104,14 @@ class AbstractAutoencoder(nn.Module):
         and `num_updates` among them -- is broadcast from the group's rank 0, one plain broadcast per tensor (once, not hot), and
         `training_step` from now on exchanges the gradients between `manual_backward` and the clip through one
         `ddp.GradientSync(params of the optimizer, group, **sync_kwargs)` per optimizer, made on its first use.  `validation_step`
-        then averages its logs over the group.  The train logs stay rank-local, the learning rate is not scaled by the group's size
+        then averages its logs over the group.  After `master_weights()` the fp32 seeds / masters are broadcast as well (the gradient
+        exchange is unchanged: 16-bit gradients keep their per-dtype torch path).  The train logs stay rank-local, the learning rate is not scaled by the group's size
         and the sampler is the caller's, as with the reference's `strategy: ddp` without `--scale_lr`.  Call it on every rank,
         before the first `training_step` (optimizer state is not broadcast)."""
         from . import ddp
         written = []
-        for t in list(self.parameters()) + list(self.buffers()):
+        masters = [] if self._master is None else [m for m in map(self.master_of, self.parameters()) if m is not None]
+        for t in list(self.parameters()) + list(self.buffers()) + masters:
             ddp.broadcast(t.detach(), group)
             written.append(t)
         if ddp.world_size(group) > 1:
@@ -142,7 +150,74 @@ class AbstractAutoencoder(nn.Module):
         if self.use_ema:
             if "model_ema" in self._modules:
                 del self._modules["model_ema"]
-            self.model_ema = LitEma(self, decay=self.ema_decay)
+            if self._master is None:
+                self.model_ema = LitEma(self, decay=self.ema_decay)
+            else:
+                self.model_ema = LitEma(self, decay=self.ema_decay, fp32_shadows=True, masters=self._master["seeds"])
+                self.model_ema.to(next(self.parameters()).device)
+
+    # ---- 16-bit networks on fp32 master weights (cvvae_amd/optim.py) ----
+    def master_weights(self, dtype: torch.dtype = torch.bfloat16) -> "AbstractAutoencoder":
+        """train the networks in `dtype` (bfloat16) on fp32 master weights.  Call it on the fp32 engine after `.cuda()` and before the
+        first `training_step` (RuntimeError once the optimizers exist).  The fp32 value of every trainable parameter is kept as its
+        master's seed; `encoder`, `decoder`, `constraint_encoder`, `constraint_decoder` (where the engine has them),
+        `loss.perceptual_loss` and `loss.discriminator` are cast, the `logvar`s stay fp32; `model_ema` is rebuilt with fp32 shadows
+        taken from the seeds; `configure_optimizers` passes `master_weights=True` and hands every seed to the optimizer's
+        `seed_master`, itself, not a copy; `on_train_batch_end` averages the masters.  Save `master_state_dict()`; to resume, load it into the fp32 engine (`apply_ckpt`)
+        BEFORE this call -- the seeds are taken here, a later `load_state_dict` reaches only the 16-bit copies."""
+        if dtype == torch.float16:
+            raise NotImplementedError("master_weights(torch.float16): fp16 training needs loss scaling, which is not built "
+                                      "(the kernels and cvvae_amd.optim.AdamW take fp16; the engine does not)")
+        if dtype != torch.bfloat16:
+            raise ValueError(f"master_weights: dtype is torch.bfloat16, got {dtype}")
+        if self._opts is not None:
+            raise RuntimeError("master_weights() after the optimizers were made: call it before the first training_step")
+        if self._master is not None:
+            raise RuntimeError("master_weights() was called already")
+        if hasattr(self, "optimizer_config"):
+            self._master_optimizer_class(self.optimizer_config)
+        kept = {p: p.detach() for p in self.parameters() if p.requires_grad and p.dtype == torch.float32}   # views: no copy
+        loss = getattr(self, "loss", None)
+        nets = [getattr(self, n, None) for n in _CAST_TO_16] + [getattr(loss, n, None) for n in ("perceptual_loss", "discriminator")]
+        for net in nets:
+            if net is not None:
+                net.to(dtype)      # the Parameter objects stay, their fp32 storage lives on in `kept`
+        self._master = {"dtype": dtype, "seeds": {p: t for p, t in kept.items() if p.dtype == dtype}}
+        self._build_ema()
+        return self
+
+    @staticmethod
+    def _master_optimizer_class(cfg):
+        cls = get_obj_from_str(cfg["target"])
+        try:
+            takes = "master_weights" in inspect.signature(cls).parameters
+        except (TypeError, ValueError):
+            takes = False
+        if not takes:
+            raise ValueError(f"master_weights(): optimizer_config.target {cfg['target']!r} does not take `master_weights`; "
+                             "use cvvae_amd.optim.AdamW")
+        return cls
+
+    def master_of(self, p: torch.Tensor) -> Optional[torch.Tensor]:
+        """the fp32 master of parameter p: the optimizer's, before its first step the seed; None for a parameter without one (the
+        engine never called master_weights(), or p stayed fp32 or is frozen)"""
+        if self._master is None:
+            return None
+        for opt in self._opts or ():
+            m = opt.master(p)
+            if m is not None:
+                return m
+        return self._master["seeds"].get(p)
+
+    def master_state_dict(self) -> Dict[str, torch.Tensor]:
+        """`state_dict()` with every trainable parameter replaced by its fp32 master (before the first step: its seed): same keys,
+        what a training script saves and cvvae_amd/checkpoint.py converts"""
+        sd = self.state_dict()
+        for name, p in self.named_parameters():
+            m = self.master_of(p) if p.requires_grad else None
+            if m is not None:
+                sd[name] = m.detach()
+        return sd
 
     def apply_ckpt(self, ckpt: Union[None, str, dict]):
         if ckpt is None:
@@ -167,7 +242,10 @@ class AbstractAutoencoder(nn.Module):
 
     def on_train_batch_end(self, *args, **kwargs):
         if self.use_ema:
-            self.model_ema(self)
+            if self._master is None:
+                self.model_ema(self)
+            else:
+                self.model_ema(self, masters=self.master_of)
 
     @contextmanager
     def ema_scope(self, context=None):
@@ -187,7 +265,15 @@ class AbstractAutoencoder(nn.Module):
         raise NotImplementedError("decode()-method of abstract base class called")
 
     def instantiate_optimizer_from_config(self, params, lr, cfg):
-        return get_obj_from_str(cfg["target"])(params, lr=lr, **cfg.get("params", dict()))
+        if self._master is None:
+            return get_obj_from_str(cfg["target"])(params, lr=lr, **cfg.get("params", dict()))
+        opt = self._master_optimizer_class(cfg)(params, lr=lr, **dict(cfg.get("params", dict()), master_weights=True))
+        for group in opt.param_groups:
+            for p in group["params"]:
+                seed = self._master["seeds"].get(p)
+                if seed is not None:
+                    opt.seed_master(p, seed)
+        return opt
 
     def instantiate_scheduler_from_config(self, optimizer, cfg):
         return get_obj_from_str(cfg["target"])(optimizer=optimizer, **cfg.get("params", dict()))

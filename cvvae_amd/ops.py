@@ -1639,6 +1639,41 @@ def mt_adamw(mtl: MultiTensorList, lr: float, beta1: float, beta2: float, eps: f
                                _mt_coef(coef, mtl) if coef is not None else None, _stream(mtl.table)), "cvvae_mt_adamw")
 
 
+def mt_adamw_master(mtl: MultiTensorList, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
+                    coef: Optional[torch.Tensor] = None) -> None:
+    """mt_adamw for a list of 16-bit parameters on fp32 master weights (include/cvvae.h cvvae_mt_adamw_master): mtl.dtype (bf16 or
+    fp16) is the type of g and p; m, v and the masters -- the list's `shadow` field -- are fp32.  Masters, m and v are updated as
+    mt_adamw updates p, m and v, and p is rewritten as the new master rounded to nearest even, in the same pass"""
+    lib, dt, chunks, table, n = _mt_args(mtl, ("g", "p", "m", "v", "shadow"))
+    if mtl.step_size is None:
+        raise ValueError("MultiTensorList: step_size / bias2_sqrt were never set")
+    L.check(lib.cvvae_mt_adamw_master(dt, chunks, table, n, float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                                      _mt_coef(coef, mtl) if coef is not None else None, _stream(mtl.table)), "cvvae_mt_adamw_master")
+
+
+def mt_sumsq(mtl: MultiTensorList, partials: torch.Tensor) -> None:
+    """the first stage of mt_grad_norm for a list of any float dtype (include/cvvae.h cvvae_mt_sumsq): one fp32 partial per chunk into
+    partials[0, n_chunks), an fp32 DEVICE tensor -- usually a slice of the workspace that the lists of one mixed-dtype norm share"""
+    lib, dt, chunks, table, n = _mt_args(mtl, ("g",))
+    if (partials.dtype != torch.float32 or partials.device != mtl.table.device or not partials.is_contiguous()
+            or partials.numel() < n):
+        raise ValueError("partials: a contiguous fp32 tensor on the list's device with an element per chunk")
+    L.check(lib.cvvae_mt_sumsq(dt, chunks, table, n, partials.data_ptr(), _stream(mtl.table)), "cvvae_mt_sumsq")
+
+
+def mt_norm_finish(partials: torch.Tensor, max_norm: float) -> torch.Tensor:
+    """the second stage (include/cvvae.h cvvae_mt_norm_finish): all of `partials` (fp32, DEVICE, written by mt_sumsq) merged in index
+    order -> fp32 DEVICE tensor [2] = the norm and coef = min(1, max_norm / (norm + 1e-6)), as mt_grad_norm.  No host synchronisation."""
+    _need_gpu(partials)
+    if partials.dtype != torch.float32 or not partials.is_contiguous():
+        raise ValueError("partials: a contiguous fp32 tensor")
+    out2 = torch.empty(2, dtype=torch.float32, device=partials.device)
+    ws = partials if partials.numel() else torch.zeros(1, dtype=torch.float32, device=partials.device)   # (a non-NULL pointer)
+    L.check(L.load().cvvae_mt_norm_finish(ws.data_ptr(), partials.numel(), float(max_norm), out2.data_ptr(), _stream(partials)),
+            "cvvae_mt_norm_finish")
+    return out2
+
+
 def mt_ema(mtl: MultiTensorList, one_minus_decay: float) -> None:
     """shadow <- shadow - one_minus_decay (shadow - p) over the list"""
     lib, dt, chunks, table, n = _mt_args(mtl, ("p", "shadow"))

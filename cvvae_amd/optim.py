@@ -16,7 +16,17 @@ Differences from clip_grad_norm_ + torch.optim.AdamW.step:
 A param group runs on the kernels when every parameter of it that has a gradient is a dense, contiguous fp32 tensor on a ROCm device
 (and `fused` was not asked for); any other group -- CPU tensors, 16-bit parameters, for which torch keeps 16-bit moments -- takes
 torch's own path unchanged.  amsgrad / maximize / capturable / differentiable have no kernel: a group that asks for one and holds a
-parameter the kernels would take is refused at construction."""
+parameter the kernels would take is refused at construction.
+
+16-bit parameters: `master_weights=True` (keyword-only, default False: nothing above changes, a 16-bit group takes torch's step bit
+for bit) trains dense contiguous bf16 / fp16 device parameters on fp32 master weights.  A bf16 weight of size 1 cannot take an update
+of 4e-5 (half an ulp is 3.9e-3): torch's step on such a group rounds every update away.  With the keyword the optimizer owns, per
+16-bit parameter, `master` (fp32; seeded by `seed_master(p, fp32_tensor)` before the first step, else `p.float()`), fp32 `exp_avg` /
+`exp_avg_sq` and torch's CPU `step`; cvvae_mt_adamw_master updates the three in fp32 and rewrites p as the rounded master in the
+same pass, the fp32 tensors of the same group go through cvvae_mt_adamw, and `max_grad_norm` reduces ONE norm over the mixed list
+(cvvae_mt_sumsq per dtype, fp32 partials first, cvvae_mt_norm_finish).  `master(p)` looks a master up.  state_dict() carries the
+fp32 state; load_state_dict() keeps it fp32 (torch's would cast it to the parameter's dtype), takes a plain torch.optim.AdamW state
+(moments upcast, master = p) and then writes p <- round(master): the optimizer state is the source of truth."""
 import math
 from typing import Iterable, List, Optional, Union
 
@@ -27,8 +37,12 @@ from . import ops
 _NO_KERNEL = ("amsgrad", "maximize", "capturable", "differentiable")
 
 
-def _kernel_tensor(t: torch.Tensor) -> bool:
-    return t.is_cuda and t.dtype == torch.float32 and not t.is_sparse and t.is_contiguous()
+_MASTER_DTYPES = (torch.bfloat16, torch.float16)
+_MASTER_STATE = ("exp_avg", "exp_avg_sq", "master")
+
+
+def _kernel_tensor(t: torch.Tensor, dtypes=(torch.float32,)) -> bool:
+    return t.is_cuda and t.dtype in dtypes and not t.is_sparse and t.is_contiguous()
 
 
 class _Lists:
@@ -38,24 +52,27 @@ class _Lists:
     def __init__(self, keep: int = 8):
         self.keep, self.d = keep, {}
 
-    def get(self, tag, tensors) -> "ops.MultiTensorList":
-        key = (tag,) + tuple(id(t) for t in tensors)
+    def get(self, tag, tensors, dtype: torch.dtype = torch.float32) -> "ops.MultiTensorList":
+        key = (tag, dtype) + tuple(id(t) for t in tensors)
         hit = self.d.get(key)
         if hit is None or [int(n) for n in hit.numels] != [t.numel() for t in tensors]:
             if len(self.d) >= self.keep:
                 self.d.pop(next(iter(self.d)))
-            hit = self.d[key] = ops.MultiTensorList([t.numel() for t in tensors], tensors[0].device if tensors else "cpu")
+            hit = self.d[key] = ops.MultiTensorList([t.numel() for t in tensors], tensors[0].device if tensors else "cpu", dtype)
         return hit
 
 
 class AdamW(torch.optim.AdamW):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
-                 foreach=None, capturable=False, differentiable=False, fused=None, max_grad_norm: Optional[float] = None):
+                 foreach=None, capturable=False, differentiable=False, fused=None, max_grad_norm: Optional[float] = None,
+                 master_weights: bool = False):
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.last_grad_norm: Optional[torch.Tensor] = None
         self._lists = _Lists()
+        self.master_weights = bool(master_weights)
+        self._seeds = {}      # parameter -> the fp32 tensor that becomes its master at the first step
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
                          foreach=foreach, capturable=capturable, differentiable=differentiable, fused=fused)
 
@@ -63,28 +80,36 @@ class AdamW(torch.optim.AdamW):
         super().add_param_group(param_group)
         g = self.param_groups[-1]
         asked = [k for k in _NO_KERNEL if g.get(k)]
-        if asked and not g.get("fused") and any(p.is_cuda and p.dtype == torch.float32 for p in g["params"]):
+        taken = self._dtypes()
+        if asked and not g.get("fused") and any(p.is_cuda and p.dtype in taken for p in g["params"]):
             self.param_groups.pop()
-            raise NotImplementedError(f"cvvae_amd.optim.AdamW: no HIP kernel for {', '.join(asked)}=True on fp32 device parameters; "
+            what = "fp32" if len(taken) == 1 else "fp32 / 16-bit"
+            raise NotImplementedError(f"cvvae_amd.optim.AdamW: no HIP kernel for {', '.join(asked)}=True on {what} device parameters; "
                                       "use torch.optim.AdamW for this group")
+
+    def _dtypes(self):
+        """the parameter dtypes the kernels take"""
+        return (torch.float32,) + (_MASTER_DTYPES if self.__dict__.get("master_weights") else ())
 
     def __setstate__(self, state):
         super().__setstate__(state)
         self.__dict__.setdefault("max_grad_norm", None)
         self.__dict__.setdefault("last_grad_norm", None)
+        self.__dict__.setdefault("master_weights", False)
+        self.__dict__.setdefault("_seeds", {})
         self._lists = _Lists()
 
     def _on_kernels(self, group) -> bool:
         if group.get("fused") or any(group.get(k) for k in _NO_KERNEL) or torch.is_tensor(group["lr"]):
             return False
-        seen = None
+        seen, dtypes = None, self._dtypes()
         for p in group["params"]:
             g = p.grad
             if g is None:
                 continue
             if g.is_sparse:
                 raise RuntimeError("Adam does not support sparse gradients, please consider SparseAdam instead")
-            if not (_kernel_tensor(p) and _kernel_tensor(g) and g.device == p.device and seen in (None, p.device)):
+            if not (_kernel_tensor(p, dtypes) and _kernel_tensor(g, (p.dtype,)) and g.device == p.device and seen in (None, p.device)):
                 return False
             seen = p.device
         return seen is not None
@@ -102,9 +127,7 @@ class AdamW(torch.optim.AdamW):
             with_grad = [p for g in groups for p in g["params"] if p.grad is not None]
             devices = {p.device for p in with_grad}
             if with_grad and len(devices) == 1 and all(k or not any(p.grad is not None for p in g["params"]) for k, g in zip(on_kernels, groups)):
-                mtl = self._lists.get("norm", with_grad).set(g=[p.grad for p in with_grad])
-                out2 = ops.mt_grad_norm(mtl, self.max_grad_norm)
-                mtl.release("g")
+                out2 = self._norm(with_grad)
                 self.last_grad_norm, coef = out2[0], out2[1]
             elif with_grad:
                 # a group the kernels do not take: torch's clip (it scales the gradients in place), then unclipped steps
@@ -116,7 +139,61 @@ class AdamW(torch.optim.AdamW):
                 self._torch_step(group)
         return loss
 
+    def _norm(self, with_grad):
+        """-> the device tensor [norm, coef] over the gradients of `with_grad`: one launch pair for an fp32 list; for a mixed one a
+        partial per chunk of each dtype's list side by side in one workspace (fp32 first, then bf16, then fp16) and one merge"""
+        by_dtype = [(dt, [p for p in with_grad if p.dtype == dt]) for dt in self._dtypes()]
+        by_dtype = [(dt, ps) for dt, ps in by_dtype if ps]
+        if [dt for dt, _ in by_dtype] == [torch.float32]:
+            mtl = self._lists.get("norm", with_grad).set(g=[p.grad for p in with_grad])
+            out2 = ops.mt_grad_norm(mtl, self.max_grad_norm)
+            mtl.release("g")
+            return out2
+        lists = [self._lists.get("norm", ps, dt).set(g=[p.grad for p in ps]) for dt, ps in by_dtype]
+        partials = torch.empty(sum(m.n_chunks for m in lists), dtype=torch.float32, device=with_grad[0].device)
+        at = 0
+        for m in lists:
+            ops.mt_sumsq(m, partials[at:at + m.n_chunks])
+            m.release("g")
+            at += m.n_chunks
+        return ops.mt_norm_finish(partials, self.max_grad_norm)
+
+    # ---- fp32 master weights of 16-bit parameters ----
+    def seed_master(self, p: torch.Tensor, value: torch.Tensor) -> None:
+        """`value` (fp32, p's shape and device, contiguous) becomes p's master at the first step, itself, not a copy"""
+        if not self.master_weights:
+            raise RuntimeError("seed_master: this optimizer was built without master_weights=True")
+        if "master" in self.state.get(p, {}):
+            raise RuntimeError("seed_master: the parameter has a master already; seeds are taken before the first step")
+        if value.dtype != torch.float32 or value.shape != p.shape or value.device != p.device or not value.is_contiguous():
+            raise ValueError("seed_master: a contiguous fp32 tensor of the parameter's shape on its device")
+        self._seeds[p] = value.detach() if value.requires_grad else value
+
+    def master(self, p: torch.Tensor) -> Optional[torch.Tensor]:
+        """the fp32 master of p: the optimizer state's, before the first step the seed; None for a parameter without one"""
+        m = self.state.get(p, {}).get("master")
+        return m if m is not None else self._seeds.get(p)
+
+    def _master_state(self, p) -> dict:
+        """p's state as the master pass needs it (made, or completed from torch's: moments upcast, master from the seed or p)"""
+        st = self.state[p]
+        if "step" not in st:
+            st["step"] = torch.tensor(0.0, dtype=torch.float32)
+        for k in ("exp_avg", "exp_avg_sq"):
+            t = st.get(k)
+            if t is None:
+                st[k] = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
+            elif t.dtype != torch.float32 or not t.is_contiguous():
+                st[k] = t.float().contiguous()
+        if "master" not in st:
+            seed = self._seeds.pop(p, None)
+            st["master"] = seed if seed is not None else p.detach().float()
+        return st
+
     def _kernel_step(self, group, coef):
+        for p in group["params"]:
+            if p.grad is not None and p.dtype in _MASTER_DTYPES:
+                self._master_state(p)
         params: List[torch.Tensor] = []
         grads: List[torch.Tensor] = []
         exp_avgs: List[torch.Tensor] = []
@@ -129,13 +206,43 @@ class AdamW(torch.optim.AdamW):
         t = torch.stack(steps).tolist()                                            # CPU tensors: no device synchronisation
         step_size = [lr / (1.0 - beta1 ** s) for s in t]
         bias2_sqrt = [math.sqrt(1.0 - beta2 ** s) for s in t]
-        mtl = self._lists.get(id(group["params"]), params)
-        mtl.set(step_size=step_size, bias2_sqrt=bias2_sqrt, g=grads, p=params, m=exp_avgs, v=exp_avg_sqs)
-        ops.mt_adamw(mtl, lr, beta1, beta2, float(group["eps"]), float(group["weight_decay"]), coef)
-        mtl.release("g")
+        hyper = (lr, beta1, beta2, float(group["eps"]), float(group["weight_decay"]), coef)
+        for dt in self._dtypes():
+            sel = [i for i, p in enumerate(params) if p.dtype == dt]
+            if not sel:
+                continue
+            pick = lambda xs: [xs[i] for i in sel]  # noqa: E731
+            fields = dict(g=pick(grads), p=pick(params), m=pick(exp_avgs), v=pick(exp_avg_sqs))
+            if dt != torch.float32:
+                fields["shadow"] = [self.state[p]["master"] for p in fields["p"]]
+            mtl = self._lists.get(id(group["params"]), fields["p"], dt)
+            mtl.set(step_size=pick(step_size), bias2_sqrt=pick(bias2_sqrt), **fields)
+            (ops.mt_adamw if dt == torch.float32 else ops.mt_adamw_master)(mtl, *hyper)
+            mtl.release("g")
         # every other writer of a parameter moves its version counter: the weight caches, the autocast copies and grad3d's
         # forward / backward check key on it
         torch.autograd.graph.increment_version(params)
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)   # casts every floating state tensor but `step` to the parameter's dtype
+        if not self.master_weights:
+            return
+        saved = [i for g in state_dict["param_groups"] for i in g["params"]]
+        mine = [p for g in self.param_groups for p in g["params"]]
+        with torch.no_grad():
+            for i, p in zip(saved, mine):
+                given = state_dict["state"].get(i)
+                if given is None or not _kernel_tensor(p, _MASTER_DTYPES):
+                    continue
+                st = self.state[p]
+                for k in _MASTER_STATE:   # from what was given, not from the cast copies
+                    if k in given:
+                        st[k] = given[k].detach().to(device=p.device, dtype=torch.float32, copy=True).contiguous()
+                self._seeds.pop(p, None)
+                if "master" not in st:    # a torch.optim.AdamW state
+                    st["master"] = p.detach().float()
+                self._master_state(p)
+                p.copy_(st["master"])     # round to nearest even; moves p's version counter
 
     def _torch_step(self, group):
         """torch.optim.AdamW.step for this one group"""

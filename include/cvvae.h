@@ -653,6 +653,20 @@ int cvvae_conv333_s2_dgrad_small(int32_t dtype, const void* gy, int64_t gy_pix_s
  * The quotient is the correctly rounded IEEE fp32 division (what DistributedDataParallel applies before its sum), NOT a product with
  * a reciprocal: the two differ in the last bit for a divisor such as 3.  divisor must be > 0 and finite (else CVVAE_EINVAL).  g and
  * shadow of a tensor may be the same address (element k is read, then written, by one thread).  An addition to ABI 14.
+ *
+ * 16-bit parameters on fp32 master weights (additions to ABI 14; the entries above keep refusing 16-bit lists):
+ * cvvae_mt_adamw_master (reads g; updates master, m, v; writes p): dtype is CVVAE_BF16 or CVVAE_F16 and is the type of g and p ONLY; m,
+ * v and the master weights are fp32, and the master's pointer travels in the `shadow` field of cvvae_mt_tensor (the struct keeps its
+ * layout).  G = coef float(g); then cvvae_mt_adamw's arithmetic with the master in the place of p -- the same FMAs: master, m and v get
+ * the bits cvvae_mt_adamw gives on fp32 copies -- and p <- the new master rounded to nearest even.  g is not written.  28 bytes per
+ * parameter, as the fp32 pass.  2-byte alignment is enough for g and p, 4-byte for the others; a group of eight moves as one 16-byte
+ * vector where that operand is 16-byte aligned, decided per operand.  CVVAE_F32 and unknown dtypes: CVVAE_EUNSUPPORTED; the other
+ * argument checks are cvvae_mt_adamw's.
+ * cvvae_mt_sumsq + cvvae_mt_norm_finish: the two stages of cvvae_mt_grad_norm as entries of their own, same order of summation, for ONE
+ * norm over a list of mixed dtypes.  cvvae_mt_sumsq (dtype CVVAE_F32 / BF16 / F16 = the type of g) writes one partial per chunk to
+ * partials[0, n_chunks): the caller lays the lists' partials side by side in one workspace (fp32 list first, then the 16-bit ones) and
+ * cvvae_mt_norm_finish merges all n_partials of them into out2 = {norm, coef} exactly as the second stage above (NaN included).  On an
+ * fp32 list the pair gives the bits of cvvae_mt_grad_norm; on a 16-bit list the bits of the fp32 list of float(g).
  */
 #define CVVAE_MT_CHUNK 8192                 /* elements; a multiple of the loss kernels' 2048-element tile */
 #define CVVAE_MT_MAX_CHUNKS (1LL << 31)
@@ -666,7 +680,7 @@ typedef struct cvvae_mt_tensor {
   void* p;      /* parameter */
   void* m;      /* exp_avg */
   void* v;      /* exp_avg_sq */
-  void* shadow; /* EMA of p */
+  void* shadow; /* EMA of p; cvvae_mt_pack: the bucket slot; cvvae_mt_adamw_master: the fp32 master of p */
   float step_size;
   float bias2_sqrt;
 } cvvae_mt_tensor;
@@ -681,6 +695,11 @@ int cvvae_mt_ema(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_ten
                  void* stream);
 int cvvae_mt_pack(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float divisor,
                   void* stream);
+int cvvae_mt_adamw_master(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, double lr,
+                          double beta1, double beta2, double eps, double weight_decay, const float* coef_dev, void* stream);
+int cvvae_mt_sumsq(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float* partials,
+                   void* stream);
+int cvvae_mt_norm_finish(const float* partials, int64_t n_partials, float max_norm, float* out2, void* stream);
 
 /*
  * Per-frame reconstruction metrics of two clips on the 8-bit scale, data_range = 255 (cvvae_amd/metrics.py; csrc/metrics_kernels.hip):

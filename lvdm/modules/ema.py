@@ -7,7 +7,15 @@ the parameter with the dots removed (`m_name2s_name`); `cvvae_amd/checkpoint.py 
 
 `copy_to` / `restore` write through `.data` (autograd leaves stay untouched) and then move the written parameters' version counters,
 as every other writer of a parameter does: the weight caches of cvvae_amd (engine.WeightCache, keyed on `_version`) see the swap
-without a checksum pass or `refresh_weights()`."""
+without a checksum pass or `refresh_weights()`.
+
+16-bit models: `LitEma(model, decay, use_num_upates, fp32_shadows=True, masters=None)` keeps the shadow of a bf16 / fp16 parameter in
+fp32 -- a clone of `masters[p]` where that mapping (parameter -> fp32 tensor) has one, else `p.float()`; a 16-bit shadow cannot take a
+step of (1 - 0.9999)(s - p).  The module's fp32 buffers, `decay` among them (0.9999 is 1.0 in bf16), then stay fp32 through
+`.to(dtype)` / `.half()` / `.bfloat16()`; devices still move.  `forward(model, masters=fn)` reads `fn(p)` instead of `p` wherever the
+callable returns a tensor (the optimizer's fp32 master weights: cvvae_amd.optim.AdamW.master), so the average follows the weights
+the optimizer holds and not their 16-bit roundings; it is the same cvvae_mt_ema launch, on fp32 operands.  Names and keys are as
+above.  Without the keyword nothing changes."""
 import numpy as np
 import torch
 from torch import nn
@@ -21,18 +29,24 @@ def _on_kernel(p: torch.Tensor, s: torch.Tensor) -> bool:
 
 
 class LitEma(nn.Module):
-    def __init__(self, model, decay=0.9999, use_num_upates=True):
+    def __init__(self, model, decay=0.9999, use_num_upates=True, *, fp32_shadows=False, masters=None):
         super().__init__()
         if decay < 0.0 or decay > 1.0:
             raise ValueError("Decay must be between 0 and 1")
         self.m_name2s_name = {}
+        self.fp32_shadows = bool(fp32_shadows)
         self.register_buffer("decay", torch.tensor(decay, dtype=torch.float32))
         self.register_buffer("num_updates", torch.tensor(0 if use_num_upates else -1, dtype=torch.int))
         for name, p in model.named_parameters():
             if p.requires_grad:
                 s_name = name.replace(".", "")  # '.' is not allowed in buffer names
                 self.m_name2s_name[name] = s_name
-                self.register_buffer(s_name, p.clone().detach().data)
+                if self.fp32_shadows and p.dtype in (torch.bfloat16, torch.float16):
+                    seed = None if masters is None else masters.get(p)
+                    shadow = p.detach().float() if seed is None else seed.detach().to(device=p.device, dtype=torch.float32, copy=True)
+                else:
+                    shadow = p.clone().detach().data
+                self.register_buffer(s_name, shadow)
         self.collected_params = []
         self._host = None     # (decay as fp32, num_updates) mirrored on the host: forward() never reads the device buffers back
         self._list = None     # (parameter ids, MultiTensorList)
@@ -62,7 +76,7 @@ class LitEma(nn.Module):
         return out
 
     @torch.no_grad()
-    def forward(self, model):
+    def forward(self, model, masters=None):
         host = self._mirror()
         decay = host[0]
         if host[1] >= 0:
@@ -72,7 +86,9 @@ class LitEma(nn.Module):
             decay = min(decay, np.float32(1 + host[1]) / np.float32(10 + host[1]))
         one_minus_decay = float(np.float32(1.0) - decay)
         fused, rest = [], []
-        for pair in self._pairs(model):
+        for p, s in self._pairs(model):
+            src = masters(p) if masters is not None else None
+            pair = (p if src is None else src, s)
             (fused if _on_kernel(*pair) else rest).append(pair)
         if fused and len({p.device for p, _ in fused}) > 1:
             rest, fused = rest + fused, []
@@ -107,4 +123,12 @@ class LitEma(nn.Module):
 
     def _apply(self, fn, *args, **kwargs):
         self._list = None  # .to() / .cuda() replace the shadows
-        return super()._apply(fn, *args, **kwargs)
+        if not self.fp32_shadows:
+            return super()._apply(fn, *args, **kwargs)
+
+        def device_only(t):
+            out = fn(t)
+            if t.dtype == torch.float32 and out.dtype != torch.float32:
+                out = t.to(out.device)
+            return out
+        return super()._apply(device_only, *args, **kwargs)

@@ -9,7 +9,15 @@ the three taking turns call by call in ONE process, each with its own parameters
     timeout -k 10 600 python tools/update_step.py                 # writes profiles/update_step.json
 
 Each figure is the median over `--iters` updates of the time between two device events around the update (so host time that the
-device does not hide is in it), after `--warmup` untimed updates.  The three passes of (a) are also timed alone, for the achieved
+device does not hide is in it), after `--warmup` untimed updates.
+
+    timeout -k 10 600 python tools/update_step.py --master        # writes profiles/update_step_master.json
+
+`--master` measures 16-bit training on the same parameter sets cast to bf16 (bf16 gradients): `master` is
+cvvae_amd.optim.AdamW(max_grad_norm=1.0, master_weights=True).step() + LitEma(fp32_shadows=True) reading the masters, against `foreach`
+/ `fused` on the bf16 tensors -- `foreach` is what a bf16 engine runs without master weights: torch's clip, torch's 16-bit AdamW, the EMA
+loop on bf16 shadows.  Alone: the AdamW-master pass against the fp32 AdamW pass on equal element counts (both move 28 bytes per
+parameter), the two-stage norm of bf16 gradients (2 bytes per parameter) and the EMA over the masters.  The three passes of (a) are also timed alone, for the achieved
 bytes/s of each kernel: 4 (norm) + 28 (AdamW) + 12 (EMA) = 44 bytes per parameter is what the update has to move, against 6.3e12
 bytes/s of achievable HBM bandwidth.  Launches of (a) are counted at the wrappers (cvvae_mt_grad_norm is two kernels, the others one;
 plus the pointer-table copies and LitEma's num_updates increment); torch's are not counted here (a kernel trace is a run of its
@@ -103,6 +111,78 @@ def rates(run, n_params, bytes_per_param):
     return run
 
 
+def measure_master(shapes, warmup, iters):
+    """the --master mode: the same shapes in bf16"""
+    dt = torch.bfloat16
+    gen = torch.Generator().manual_seed(5)
+    n_params = sum(int(torch.Size(s).numel()) for s in shapes)
+    out = {"parameters": n_params, "tensors": len(shapes), "chunks": sum(-(-int(torch.Size(s).numel()) // _lib.MT_CHUNK) for s in shapes)}
+    sets = {}
+    for path in ("master", "foreach", "fused", "fp32"):
+        net = Params(shapes, torch.Generator().manual_seed(6)).cuda()
+        if path != "fp32":
+            net.to(dt)
+        for p in net.parameters():
+            p.grad = (torch.randn(p.shape, generator=gen) * 0.01).to(p.dtype).cuda()
+        sets[path] = net
+    fns = {}
+    net = sets["master"]
+    opt = AdamW(net.parameters(), max_grad_norm=1.0, master_weights=True, **ADAMW)
+    opt.step()                                               # the masters exist from here on
+    ema = LitEma(net, fp32_shadows=True, masters={p: opt.master(p) for p in net.parameters()})
+
+    def master_update():
+        opt.step()
+        ema(net, masters=opt.master)
+    fns["master"] = master_update
+    for path, kw in (("foreach", dict(foreach=True)), ("fused", dict(fused=True))):
+        try:
+            t_opt = torch.optim.AdamW(sets[path].parameters(), **ADAMW, **kw)
+        except (RuntimeError, ValueError) as e:
+            out[path] = {"refused": str(e)}
+            continue
+        ps = list(sets[path].parameters())
+        shadows = [p.detach().clone() for p in ps]
+        decay, num_updates = torch.tensor(0.9999, device="cuda"), torch.tensor(0, dtype=torch.int, device="cuda")
+
+        def torch_update(ps=ps, t_opt=t_opt, shadows=shadows, decay=decay, num_updates=num_updates):
+            torch.nn.utils.clip_grad_norm_(ps, 1.0)
+            t_opt.step()
+            loop_ema(ps, shadows, decay, num_updates)
+        fns[path] = torch_update
+    run = timed(fns, warmup, iters)
+    bytes_per_param = 2 + 28 + 12                            # the norm reads 2-byte gradients
+    for k, v in run.items():
+        out[k] = rates(v, n_params, bytes_per_param)
+    out["foreach_over_master"] = run["foreach"]["median_ms"] / run["master"]["median_ms"]
+
+    # the passes alone: the master pass against the fp32 pass on equal element counts, taking turns
+    ps = list(net.parameters())
+    st = [opt.state[p] for p in ps]
+    scal = dict(step_size=[ADAMW["lr"] / (1 - 0.9 ** 50)] * len(ps), bias2_sqrt=[(1 - 0.98 ** 50) ** 0.5] * len(ps))
+    numels = [p.numel() for p in ps]
+    m16 = ops.MultiTensorList(numels, "cuda", dt).set(g=[p.grad for p in ps], p=ps, m=[s["exp_avg"] for s in st],
+                                                      v=[s["exp_avg_sq"] for s in st], shadow=[s["master"] for s in st], **scal)
+    ema16 = ops.MultiTensorList(numels, "cuda").set(p=[s["master"] for s in st],
+                                                   shadow=[getattr(ema, ema.m_name2s_name[n]) for n, _ in net.named_parameters()])
+    qs = list(sets["fp32"].parameters())
+    m32 = ops.MultiTensorList(numels, "cuda").set(g=[q.grad for q in qs], p=qs, m=[torch.zeros_like(q) for q in qs],
+                                                  v=[torch.zeros_like(q) for q in qs], **scal)
+    coef = torch.ones(1, device="cuda")
+    partials = torch.empty(max(m16.n_chunks, 1), dtype=torch.float32, device="cuda")
+    hp = (ADAMW["lr"], 0.9, 0.98, ADAMW["eps"], ADAMW["weight_decay"], coef)
+
+    def norm16():
+        ops.mt_sumsq(m16, partials)
+        ops.mt_norm_finish(partials[:m16.n_chunks], 1.0)
+    kern = timed({"adamw_master": lambda: ops.mt_adamw_master(m16, *hp), "adamw_fp32": lambda: ops.mt_adamw(m32, *hp),
+                  "sumsq_norm_finish": norm16, "ema": lambda: ops.mt_ema(ema16, 1e-4)}, warmup, iters)
+    per = {"adamw_master": 28, "adamw_fp32": 28, "sumsq_norm_finish": 2, "ema": 12}
+    out["hip_kernels"] = {k: rates(v, n_params, per[k]) for k, v in kern.items()}
+    out["adamw_master_over_adamw_fp32"] = kern["adamw_master"]["median_ms"] / kern["adamw_fp32"]["median_ms"]
+    return out
+
+
 def measure(shapes, warmup, iters):
     gen = torch.Generator().manual_seed(5)
     n_params = sum(int(torch.Size(s).numel()) for s in shapes)
@@ -170,14 +250,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--sets", default="codec,discriminator")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "update_step.json"))
+    ap.add_argument("--master", action="store_true", help="bf16 parameters on fp32 master weights (profiles/update_step_master.json)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "update_step_master.json" if a.master else "update_step.json")
     if not torch.cuda.is_available():
         raise SystemExit("tools/update_step.py measures on an MI355X; no GPU found (there is no CPU path)")
     torch.cuda.set_device(0)
     import cvvae_amd
     from cvvae_amd.discriminator import get_cvvae_discriminator
-    res = {"update": "clip_gradients(1.0, 'norm') + AdamW step + LitEma, fp32, yaml hyper-parameters", "warmup": a.warmup,
+    what = "bf16 parameters and gradients; master = fp32 master weights, moments and shadows" if a.master else "fp32"
+    res = {"update": f"clip_gradients(1.0, 'norm') + AdamW step + LitEma, {what}, yaml hyper-parameters", "warmup": a.warmup,
            "device": torch.cuda.get_device_name(0), "kernel_sources": _lib.source_fingerprint(), "hbm_bytes_per_s": HBM_BYTES_PER_S,
            "timing": "device events around each update, paths interleaved in one process", "sets": {}}
     for name in a.sets.split(","):
@@ -188,7 +271,7 @@ def main():
             shapes = [tuple(p.shape) for p in get_cvvae_discriminator().parameters()]
         else:
             raise SystemExit(f"unknown parameter set {name!r}")
-        res["sets"][name] = measure(shapes, a.warmup, a.iters)
+        res["sets"][name] = (measure_master if a.master else measure)(shapes, a.warmup, a.iters)
         print(name, json.dumps(res["sets"][name]), flush=True)
         torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
