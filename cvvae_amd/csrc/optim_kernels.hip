@@ -1,23 +1,26 @@
 // optim_kernels.hip -- the parameter update of a training iteration (cvvae_amd/optim.py, lvdm/modules/ema.py) as multi-tensor passes
-// over a LIST of fp32 tensors: the L2 norm of all gradients with the clip coefficient, g <- coef g, AdamW with the coefficient applied
+// over a LIST of tensors: the L2 norm of all gradients with the clip coefficient, g <- coef g, AdamW with the coefficient applied
 // in flight, the EMA of the weights, and the pack pass of the data-parallel gradient exchange (cvvae_amd/ddp.py: g / world size into
-// the slots of one flat bucket).  16-bit networks train on fp32 master weights through adamw_master_kernel: 16-bit g and p, fp32
-// master / m / v, the 16-bit parameter rewritten from the new master in the same pass; sumsq_kernel reads fp32 or 16-bit gradients, so
-// one norm covers a mixed list (cvvae_mt_sumsq per dtype into one workspace, then cvvae_mt_norm_finish).  gfx950 only.  All of them
-// are HBM-bound: plain C++.
+// the slots of one flat bucket).  adamw_kernel<T> is the one AdamW pass: T = float updates fp32 parameters in place; T = a 16-bit
+// type trains a 16-bit network on fp32 master weights (16-bit g and p, fp32 master / m / v, the 16-bit parameter rewritten from the
+// new master in the same pass).  sumsq_kernel reads fp32 or 16-bit gradients, so one norm covers a mixed list (cvvae_mt_sumsq per
+// dtype into one workspace, then cvvae_mt_norm_finish).  gfx950 only.  All of them are HBM-bound: plain C++.
 //
-// Geometry.  The list is cut into chunks of at most CHUNK elements that never straddle two tensors (cvvae_mt_chunk: tensor index,
-// first element, length); the tensors' base pointers and per-tensor scalars sit in a second table (cvvae_mt_tensor).  One workgroup
-// of 256 threads takes a chunk, workgroup w walking chunks w, w + grid, ...  Inside a chunk group j = elements [8j, 8j + 8) belongs to
-// thread j % 256; a group moves as two 16-byte vectors per operand when it is whole and that operand's address is 16-byte aligned,
-// element by element otherwise (the tail of a chunk; a tensor that starts 4 bytes into its buffer).  A group of eight 16-bit values is
-// one 16-byte vector under the same rule, decided per operand (a view that starts 2 bytes into its buffer goes element by element).
+// Geometry (for_each_chunk, for_each_group: every kernel walks the list through these two).  The list is cut into chunks of at most
+// CHUNK elements that never straddle two tensors (cvvae_mt_chunk: tensor index, first element, length); the tensors' base pointers
+// and per-tensor scalars sit in a second table (cvvae_mt_tensor).  One workgroup of 256 threads takes a chunk, workgroup w walking
+// chunks w, w + grid, ...  Inside a chunk group j = elements [8j, 8j + 8) belongs to thread j % 256; a group moves as two 16-byte
+// vectors per operand when it is whole and that operand's address is 16-byte aligned, element by element otherwise (the tail of a
+// chunk; a tensor that starts 4 bytes into its buffer).  A group of eight 16-bit values is one 16-byte vector under the same rule,
+// decided per operand (a view that starts 2 bytes into its buffer goes element by element).
 //
 // Order of summation (cvvae_mt_grad_norm).  A thread adds the squares of a group in index order, then its groups in index order;
 // the 64 lanes of a wave are merged by a butterfly, the four waves through LDS in wave order: ONE partial per chunk.  Stage 2 (one
 // workgroup) merges the partials, thread t taking t, t + 256, ... serially, then the same workgroup sum.  Nothing is atomic and the
 // grid does not enter: the norm is a function of the values and the list order alone, bit-identical from run to run.
 // Longest chain of additions: 8 (CHUNK / 2048 = 4 groups: 7 + 1 each, 32) + 6 + 3 in a chunk, ceil(n_chunks / 256) + 6 + 3 in stage 2.
+#include <type_traits>
+
 #include "pass_common.h"
 
 namespace cvvae {
@@ -30,27 +33,40 @@ constexpr int CHUNK = CVVAE_MT_CHUNK;
 constexpr int MAX_BLOCKS = 2048;     // grid cap (8 workgroups per CU), as loss_kernels.hip
 static_assert(CHUNK % TILE == 0, "a chunk is a whole number of tiles");
 
+// the chunk walk: body(c, chunk c) for the chunks of this workgroup, in index order.  What a kernel does once per chunk (its operands'
+// addresses, sumsq_kernel's workgroup sum) stands in the body, around for_each_group
+template <typename F>
+__device__ __forceinline__ void for_each_chunk(const cvvae_mt_chunk* __restrict__ chunks, long long n_chunks, F&& body) {
+  for (long long c = blockIdx.x; c < n_chunks; c += gridDim.x) body(c, chunks[c]);
+}
+// body(i, n) for the groups of this thread, in index order: elements [i, i + n) of the chunk, n = VEC but for the chunk's last group
+// The body is a lambda marked always_inline: inlined early, with ld8_n / st8_n, every operand keeps its two 16-byte accesses on the
+// whole-group path.  Left to the ordinary inliner the body is optimised on its own first, and the compiler then merges a vector
+// path's last element with the tail path's scalar load (a 12-byte access beside a 16-byte one: measured 3-7 % on the AdamW passes)
+template <typename F>
+__device__ __forceinline__ void for_each_group(const cvvae_mt_chunk& ch, F&& body) {
+  for (int i = threadIdx.x * VEC; i < ch.n; i += TILE) body(i, (ch.n - i) < VEC ? (ch.n - i) : VEC);
+}
+
 // T: the gradients' storage type; the squares and every sum are fp32, so a 16-bit list gives the bits of its fp32 copy
 template <typename T>
 __global__ __launch_bounds__(WG) void sumsq_kernel(const cvvae_mt_chunk* __restrict__ chunks, const cvvae_mt_tensor* __restrict__ tensors,
                                                    long long n_chunks, float* __restrict__ ws) {
-  for (long long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-    const cvvae_mt_chunk ch = chunks[c];
+  for_each_chunk(chunks, n_chunks, [&](long long c, const cvvae_mt_chunk& ch) {
     const T* g = (const T*)tensors[ch.tensor].g + ch.start;
     float acc = 0.f;
-    for (int i = threadIdx.x * VEC; i < ch.n; i += TILE) {
-      const int n = (ch.n - i) < VEC ? (ch.n - i) : VEC;
+    for_each_group(ch, [&](int i, int n) __attribute__((always_inline)) {
       float f[VEC];
       ld8_n(g + i, n, f);
       float s = 0.f;
 #pragma unroll
       for (int k = 0; k < VEC; ++k) s += f[k] * f[k];
       acc += s;
-    }
+    });
     acc = block_sum(acc);
     __syncthreads();  // frees block_sum's LDS slots for the next chunk
     if (threadIdx.x == 0) ws[c] = acc;
-  }
+  });
 }
 
 // out2[0] = sqrt(sum of the partials), out2[1] = min(1, max_norm / (norm + 1e-6)) with clamp's treatment of NaN: the comparison
@@ -72,77 +88,40 @@ __global__ __launch_bounds__(WG) void norm_final_kernel(const float* __restrict_
 __global__ __launch_bounds__(WG) void scale_kernel(const cvvae_mt_chunk* __restrict__ chunks, const cvvae_mt_tensor* __restrict__ tensors,
                                                    long long n_chunks, const float* __restrict__ coef_dev) {
   const float coef = coef_dev[0];
-  for (long long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-    const cvvae_mt_chunk ch = chunks[c];
+  for_each_chunk(chunks, n_chunks, [&](long long, const cvvae_mt_chunk& ch) {
     float* g = (float*)tensors[ch.tensor].g + ch.start;
-    for (int i = threadIdx.x * VEC; i < ch.n; i += TILE) {
-      const int n = (ch.n - i) < VEC ? (ch.n - i) : VEC;
+    for_each_group(ch, [&](int i, int n) __attribute__((always_inline)) {
       float f[VEC];
       ld8_n(g + i, n, f);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) f[k] = coef * f[k];
       st8_n(g + i, f, n);
-    }
-  }
+    });
+  });
 }
 
 struct AdamW {
   float beta1, one_minus_beta1, beta2, one_minus_beta2, eps, decay;  // decay = 1 - lr weight_decay
 };
 
+// T: the storage type of g and p.  float: p itself is updated.  A 16-bit type: the fp32 weights are the master (the `shadow` field),
+// and p is rewritten as the new master rounded to nearest even.  One element update for both, so master, m and v come out with the
+// bits of the fp32 pass on fp32 copies (tests/test_gpu_master_optim.py); tests/test_gpu_update_parity.py pins the bits themselves
+template <typename T>
 __global__ __launch_bounds__(WG) void adamw_kernel(const cvvae_mt_chunk* __restrict__ chunks, const cvvae_mt_tensor* __restrict__ tensors,
                                                    long long n_chunks, AdamW h, const float* __restrict__ coef_dev) {
+  constexpr bool kMaster = !std::is_same<T, float>::value;
   const float coef = coef_dev ? coef_dev[0] : 1.f;
-  for (long long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-    const cvvae_mt_chunk ch = chunks[c];
-    const cvvae_mt_tensor t = tensors[ch.tensor];
-    const float* g = (const float*)t.g + ch.start;
-    float* p = (float*)t.p + ch.start;
-    float* m = (float*)t.m + ch.start;
-    float* v = (float*)t.v + ch.start;
-    for (int i = threadIdx.x * VEC; i < ch.n; i += TILE) {
-      const int n = (ch.n - i) < VEC ? (ch.n - i) : VEC;
-      float fg[VEC], fp[VEC], fm[VEC], fv[VEC];
-      ld8_n(g + i, n, fg);
-      ld8_n(p + i, n, fp);
-      ld8_n(m + i, n, fm);
-      ld8_n(v + i, n, fv);
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) {
-        const float G = coef_dev ? coef * fg[k] : fg[k];
-        fm[k] = __builtin_fmaf(h.beta1, fm[k], h.one_minus_beta1 * G);
-        fv[k] = __builtin_fmaf(h.beta2, fv[k], h.one_minus_beta2 * (G * G));
-        const float denom = sqrtf(fv[k]) / t.bias2_sqrt + h.eps;
-        fp[k] = fp[k] * h.decay - t.step_size * (fm[k] / denom);
-      }
-      st8_n(p + i, fp, n);
-      st8_n(m + i, fm, n);
-      st8_n(v + i, fv, n);
-    }
-  }
-}
-
-// adamw_kernel for a 16-bit parameter: g and p are T, the fp32 master (the `shadow` field) stands in the place of p, and p is
-// rewritten as the new master rounded to nearest even.  The element update is adamw_kernel's, expression for expression, so that
-// both contract to the same FMAs: master, m and v come out with the bits of adamw_kernel on fp32 copies (tests/test_gpu_master_optim.py)
-template <typename T>
-__global__ __launch_bounds__(WG) void adamw_master_kernel(const cvvae_mt_chunk* __restrict__ chunks,
-                                                          const cvvae_mt_tensor* __restrict__ tensors, long long n_chunks, AdamW h,
-                                                          const float* __restrict__ coef_dev) {
-  const float coef = coef_dev ? coef_dev[0] : 1.f;
-  for (long long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-    const cvvae_mt_chunk ch = chunks[c];
+  for_each_chunk(chunks, n_chunks, [&](long long, const cvvae_mt_chunk& ch) {
     const cvvae_mt_tensor t = tensors[ch.tensor];
     const T* g = (const T*)t.g + ch.start;
-    T* p = (T*)t.p + ch.start;
-    float* w = (float*)t.shadow + ch.start;
+    float* w = (float*)(kMaster ? t.shadow : t.p) + ch.start;
     float* m = (float*)t.m + ch.start;
     float* v = (float*)t.v + ch.start;
-    for (int i = threadIdx.x * VEC; i < ch.n; i += TILE) {
-      const int n = (ch.n - i) < VEC ? (ch.n - i) : VEC;
-      float fg[VEC], fp[VEC], fm[VEC], fv[VEC];
+    for_each_group(ch, [&](int i, int n) __attribute__((always_inline)) {
+      float fg[VEC], fw[VEC], fm[VEC], fv[VEC];
       ld8_n(g + i, n, fg);
-      ld8_n(w + i, n, fp);
+      ld8_n(w + i, n, fw);
       ld8_n(m + i, n, fm);
       ld8_n(v + i, n, fv);
 #pragma unroll
@@ -151,46 +130,42 @@ __global__ __launch_bounds__(WG) void adamw_master_kernel(const cvvae_mt_chunk* 
         fm[k] = __builtin_fmaf(h.beta1, fm[k], h.one_minus_beta1 * G);
         fv[k] = __builtin_fmaf(h.beta2, fv[k], h.one_minus_beta2 * (G * G));
         const float denom = sqrtf(fv[k]) / t.bias2_sqrt + h.eps;
-        fp[k] = fp[k] * h.decay - t.step_size * (fm[k] / denom);
+        fw[k] = fw[k] * h.decay - t.step_size * (fm[k] / denom);
       }
-      st8_n(w + i, fp, n);
+      st8_n(w + i, fw, n);
       st8_n(m + i, fm, n);
       st8_n(v + i, fv, n);
-      st8_n(p + i, fp, n);
-    }
-  }
+      if constexpr (kMaster) st8_n((T*)t.p + ch.start + i, fw, n);
+    });
+  });
 }
 
 __global__ __launch_bounds__(WG) void ema_kernel(const cvvae_mt_chunk* __restrict__ chunks, const cvvae_mt_tensor* __restrict__ tensors,
                                                  long long n_chunks, float one_minus_decay) {
-  for (long long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-    const cvvae_mt_chunk ch = chunks[c];
+  for_each_chunk(chunks, n_chunks, [&](long long, const cvvae_mt_chunk& ch) {
     const cvvae_mt_tensor t = tensors[ch.tensor];
     const float* p = (const float*)t.p + ch.start;
     float* s = (float*)t.shadow + ch.start;
-    for (int i = threadIdx.x * VEC; i < ch.n; i += TILE) {
-      const int n = (ch.n - i) < VEC ? (ch.n - i) : VEC;
+    for_each_group(ch, [&](int i, int n) __attribute__((always_inline)) {
       float fp[VEC], fs[VEC];
       ld8_n(p + i, n, fp);
       ld8_n(s + i, n, fs);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) fs[k] = fs[k] - one_minus_decay * (fs[k] - fp[k]);
       st8_n(s + i, fs, n);
-    }
-  }
+    });
+  });
 }
 
 // shadow <- g / divisor (zeros for a tensor without a gradient: g NULL).  `/` is the correctly rounded fp32 division (hipcc's default;
 // the Makefile sets no fast-math flag), as in adamw_kernel.  g and shadow carry no __restrict__: they may be one address.
 __global__ __launch_bounds__(WG) void pack_kernel(const cvvae_mt_chunk* __restrict__ chunks, const cvvae_mt_tensor* __restrict__ tensors,
                                                   long long n_chunks, float divisor) {
-  for (long long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-    const cvvae_mt_chunk ch = chunks[c];
+  for_each_chunk(chunks, n_chunks, [&](long long, const cvvae_mt_chunk& ch) {
     const cvvae_mt_tensor t = tensors[ch.tensor];
     const float* g = t.g ? (const float*)t.g + ch.start : nullptr;
     float* d = (float*)t.shadow + ch.start;
-    for (int i = threadIdx.x * VEC; i < ch.n; i += TILE) {
-      const int n = (ch.n - i) < VEC ? (ch.n - i) : VEC;
+    for_each_group(ch, [&](int i, int n) __attribute__((always_inline)) {
       float f[VEC];
       if (g) {
         ld8_n(g + i, n, f);
@@ -201,26 +176,46 @@ __global__ __launch_bounds__(WG) void pack_kernel(const cvvae_mt_chunk* __restri
         for (int k = 0; k < VEC; ++k) f[k] = 0.f;
       }
       st8_n(d + i, f, n);
-    }
-  }
+    });
+  });
 }
 
-static inline int blocks_for(long long n_chunks) { return (int)(n_chunks < MAX_BLOCKS ? n_chunks : MAX_BLOCKS); }
+// ---- host side ----
+// a list kernel: the two tables and the chunk count, then the pass's own arguments
+template <typename... A>
+using ListKernel = void (*)(const cvvae_mt_chunk*, const cvvae_mt_tensor*, long long, A...);
 
-// CVVAE_OK when the launch has something to do, 1 when the list is empty (nothing to launch), else the error
-static inline int check_tables(bool dtype_ok, const void* chunks, const void* tensors, int64_t n_chunks) {
+// One list pass: `kernel` over the chunks, one workgroup per chunk up to the grid cap.  nullptr says that the entry has no kernel
+// for the list's dtype.  An empty list is no error and no launch
+template <typename... A, typename... B>
+static int launch_list(ListKernel<A...> kernel, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks,
+                       void* stream, B... args) {
   if (n_chunks < 0 || n_chunks > CVVAE_MT_MAX_CHUNKS) return CVVAE_EINVAL;
-  if (!dtype_ok) return CVVAE_EUNSUPPORTED;
-  if (n_chunks == 0) return 1;
+  if (!kernel) return CVVAE_EUNSUPPORTED;
+  if (n_chunks == 0) return CVVAE_OK;
   if (!chunks || !tensors) return CVVAE_EINVAL;
-  return CVVAE_OK;
+  const int blocks = (int)(n_chunks < MAX_BLOCKS ? n_chunks : MAX_BLOCKS);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, chunks, tensors, (long long)n_chunks, args...);
+  return launch_status();
 }
-// the fp32-only entry points
-static inline int check_list(int32_t dtype, const void* chunks, const void* tensors, int64_t n_chunks) {
-  return check_tables(dtype == CVVAE_F32, chunks, tensors, n_chunks);
+template <typename K>
+static K fp32_only(int32_t dtype, K kernel) { return dtype == CVVAE_F32 ? kernel : nullptr; }
+
+static ListKernel<float*> sumsq_for(int32_t dtype) {
+  ListKernel<float*> k = nullptr;
+  by_dtype(dtype, [&](auto tag) { k = sumsq_kernel<typename decltype(tag)::type>; });
+  return k;
 }
-static inline bool valid_adamw(double lr, double beta1, double beta2, double eps, double weight_decay) {
-  return lr >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && weight_decay >= 0.0;
+static int launch_norm_finish(const float* partials, int64_t n_partials, float max_norm, float* out2, void* stream) {
+  hipLaunchKernelGGL(norm_final_kernel, dim3(1), dim3(WG), 0, (hipStream_t)stream, partials, (long long)n_partials, max_norm, out2);
+  return launch_status();
+}
+static int launch_adamw(ListKernel<AdamW, const float*> kernel, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors,
+                        int64_t n_chunks, double lr, double beta1, double beta2, double eps, double weight_decay, const float* coef_dev,
+                        void* stream) {
+  if (!(lr >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && weight_decay >= 0.0)) return CVVAE_EINVAL;
+  const AdamW h{(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)(1.0 - lr * weight_decay)};
+  return launch_list(kernel, chunks, tensors, n_chunks, stream, h, coef_dev);
 }
 
 }  // namespace optim
@@ -236,90 +231,53 @@ size_t cvvae_mt_workspace_bytes(int64_t n_chunks) {
   return (size_t)(n_chunks > 4 ? n_chunks : 4) * sizeof(float);
 }
 
+// stage 1 on the fp32 list, then stage 2 as cvvae_mt_norm_finish runs it: over an empty list too (norm 0, coef 1)
 int cvvae_mt_grad_norm(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float max_norm,
                        void* workspace, float* out2, void* stream) {
   if (!workspace || !out2) return CVVAE_EINVAL;
-  const int rc = check_list(dtype, chunks, tensors, n_chunks);
-  if (rc < 0) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if (rc == 0)
-    hipLaunchKernelGGL(sumsq_kernel<float>, dim3(blocks_for(n_chunks)), dim3(WG), 0, s, chunks, tensors, (long long)n_chunks,
-                       (float*)workspace);
-  hipLaunchKernelGGL(norm_final_kernel, dim3(1), dim3(WG), 0, s, (const float*)workspace, (long long)n_chunks, max_norm, out2);
-  return launch_status();
+  const int rc = launch_list(fp32_only(dtype, sumsq_kernel<float>), chunks, tensors, n_chunks, stream, (float*)workspace);
+  return rc != CVVAE_OK ? rc : launch_norm_finish((const float*)workspace, n_chunks, max_norm, out2, stream);
 }
 
 int cvvae_mt_scale(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, const float* coef_dev,
                    void* stream) {
   if (!coef_dev) return CVVAE_EINVAL;
-  const int rc = check_list(dtype, chunks, tensors, n_chunks);
-  if (rc != 0) return rc < 0 ? rc : CVVAE_OK;
-  hipLaunchKernelGGL(scale_kernel, dim3(blocks_for(n_chunks)), dim3(WG), 0, (hipStream_t)stream, chunks, tensors, (long long)n_chunks,
-                     coef_dev);
-  return launch_status();
+  return launch_list(fp32_only(dtype, scale_kernel), chunks, tensors, n_chunks, stream, coef_dev);
 }
 
 int cvvae_mt_adamw(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, double lr, double beta1,
                    double beta2, double eps, double weight_decay, const float* coef_dev, void* stream) {
-  if (!valid_adamw(lr, beta1, beta2, eps, weight_decay)) return CVVAE_EINVAL;
-  const int rc = check_list(dtype, chunks, tensors, n_chunks);
-  if (rc != 0) return rc < 0 ? rc : CVVAE_OK;
-  const AdamW h{(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)(1.0 - lr * weight_decay)};
-  hipLaunchKernelGGL(adamw_kernel, dim3(blocks_for(n_chunks)), dim3(WG), 0, (hipStream_t)stream, chunks, tensors, (long long)n_chunks, h,
-                     coef_dev);
-  return launch_status();
+  return launch_adamw(fp32_only(dtype, adamw_kernel<float>), chunks, tensors, n_chunks, lr, beta1, beta2, eps, weight_decay, coef_dev,
+                      stream);
 }
 
 int cvvae_mt_adamw_master(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, double lr,
                           double beta1, double beta2, double eps, double weight_decay, const float* coef_dev, void* stream) {
-  if (!valid_adamw(lr, beta1, beta2, eps, weight_decay)) return CVVAE_EINVAL;
-  const int rc = check_tables(dtype == CVVAE_BF16 || dtype == CVVAE_F16, chunks, tensors, n_chunks);
-  if (rc != 0) return rc < 0 ? rc : CVVAE_OK;
-  const AdamW h{(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)(1.0 - lr * weight_decay)};
-  by_dtype16(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    hipLaunchKernelGGL(adamw_master_kernel<T>, dim3(blocks_for(n_chunks)), dim3(WG), 0, (hipStream_t)stream, chunks, tensors,
-                       (long long)n_chunks, h, coef_dev);
-  });
-  return launch_status();
+  ListKernel<AdamW, const float*> kernel = nullptr;
+  by_dtype16(dtype, [&](auto tag) { kernel = adamw_kernel<typename decltype(tag)::type>; });
+  return launch_adamw(kernel, chunks, tensors, n_chunks, lr, beta1, beta2, eps, weight_decay, coef_dev, stream);
 }
 
 int cvvae_mt_sumsq(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float* partials,
                    void* stream) {
   if (!partials) return CVVAE_EINVAL;
-  const int rc = check_tables(known_dtype(dtype), chunks, tensors, n_chunks);
-  if (rc != 0) return rc < 0 ? rc : CVVAE_OK;
-  by_dtype(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    hipLaunchKernelGGL(sumsq_kernel<T>, dim3(blocks_for(n_chunks)), dim3(WG), 0, (hipStream_t)stream, chunks, tensors,
-                       (long long)n_chunks, partials);
-  });
-  return launch_status();
+  return launch_list(sumsq_for(dtype), chunks, tensors, n_chunks, stream, partials);
 }
 
 int cvvae_mt_norm_finish(const float* partials, int64_t n_partials, float max_norm, float* out2, void* stream) {
   if (!partials || !out2 || n_partials < 0 || n_partials > CVVAE_MT_MAX_CHUNKS) return CVVAE_EINVAL;
-  hipLaunchKernelGGL(norm_final_kernel, dim3(1), dim3(WG), 0, (hipStream_t)stream, partials, (long long)n_partials, max_norm, out2);
-  return launch_status();
+  return launch_norm_finish(partials, n_partials, max_norm, out2, stream);
 }
 
 int cvvae_mt_ema(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float one_minus_decay,
                  void* stream) {
-  const int rc = check_list(dtype, chunks, tensors, n_chunks);
-  if (rc != 0) return rc < 0 ? rc : CVVAE_OK;
-  hipLaunchKernelGGL(ema_kernel, dim3(blocks_for(n_chunks)), dim3(WG), 0, (hipStream_t)stream, chunks, tensors, (long long)n_chunks,
-                     one_minus_decay);
-  return launch_status();
+  return launch_list(fp32_only(dtype, ema_kernel), chunks, tensors, n_chunks, stream, one_minus_decay);
 }
 
 int cvvae_mt_pack(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float divisor,
                   void* stream) {
   if (!(divisor > 0.f) || !(divisor <= 3.402823466e38f)) return CVVAE_EINVAL;
-  const int rc = check_list(dtype, chunks, tensors, n_chunks);
-  if (rc != 0) return rc < 0 ? rc : CVVAE_OK;
-  hipLaunchKernelGGL(pack_kernel, dim3(blocks_for(n_chunks)), dim3(WG), 0, (hipStream_t)stream, chunks, tensors, (long long)n_chunks,
-                     divisor);
-  return launch_status();
+  return launch_list(fp32_only(dtype, pack_kernel), chunks, tensors, n_chunks, stream, divisor);
 }
 
 }  // extern "C"

@@ -1597,12 +1597,16 @@ class MultiTensorList:
         self.uploads += 1
 
 
-def _mt_args(mtl: MultiTensorList, need):
+def _mt_pass(entry: str, mtl: MultiTensorList, need, args) -> None:
+    """one list pass, lib.<entry>(dtype, chunks, table, n_chunks, *own, stream): `args(lib)` builds and checks `own` AFTER the list's checks"""
     _need_gpu(mtl.table)
     missing = [f for f in need if f not in mtl.tensors]
     if missing:
         raise ValueError(f"MultiTensorList: fields {missing} were never set")
-    return L.load(), _dt(mtl.dtype), mtl.chunks.data_ptr(), mtl.table.data_ptr(), mtl.n_chunks
+    lib, dt = L.load(), _dt(mtl.dtype)
+    own = args(lib)   # (tensors among them go in as pointers and live until the launch is queued)
+    L.check(getattr(lib, entry)(dt, mtl.chunks.data_ptr(), mtl.table.data_ptr(), mtl.n_chunks,
+                                *[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in own], _stream(mtl.table)), entry)
 
 
 def _mt_coef(coef: torch.Tensor, mtl: MultiTensorList):
@@ -1611,32 +1615,33 @@ def _mt_coef(coef: torch.Tensor, mtl: MultiTensorList):
     return coef.data_ptr()
 
 
+def _mt_adamw(entry: str, need, mtl: MultiTensorList, lr, beta1, beta2, eps, weight_decay, coef) -> None:
+    def args(lib):
+        if mtl.step_size is None:
+            raise ValueError("MultiTensorList: step_size / bias2_sqrt were never set")
+        return (float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), _mt_coef(coef, mtl) if coef is not None else None)
+    _mt_pass(entry, mtl, need, args)
+
+
 def mt_grad_norm(mtl: MultiTensorList, max_norm: float) -> torch.Tensor:
     """-> fp32 DEVICE tensor [2]: the L2 norm of all the list's gradients taken together, and coef = min(1, max_norm / (norm + 1e-6))
     (NaN stays NaN).  Deterministic: no atomics, one partial per chunk merged in chunk order.  No host synchronisation."""
-    lib, dt, chunks, table, n = _mt_args(mtl, ("g",))
-    ws = torch.empty(int(lib.cvvae_mt_workspace_bytes(n)), dtype=torch.uint8, device=mtl.table.device)
     out2 = torch.empty(2, dtype=torch.float32, device=mtl.table.device)
-    L.check(lib.cvvae_mt_grad_norm(dt, chunks, table, n, float(max_norm), ws.data_ptr(), out2.data_ptr(), _stream(mtl.table)),
-            "cvvae_mt_grad_norm")
+    _mt_pass("cvvae_mt_grad_norm", mtl, ("g",), lambda lib: (
+        float(max_norm), torch.empty(int(lib.cvvae_mt_workspace_bytes(mtl.n_chunks)), dtype=torch.uint8, device=mtl.table.device), out2))
     return out2
 
 
 def mt_scale(mtl: MultiTensorList, coef: torch.Tensor) -> None:
     """g <- coef g in place over the list; coef: one fp32 DEVICE element"""
-    lib, dt, chunks, table, n = _mt_args(mtl, ("g",))
-    L.check(lib.cvvae_mt_scale(dt, chunks, table, n, _mt_coef(coef, mtl), _stream(mtl.table)), "cvvae_mt_scale")
+    _mt_pass("cvvae_mt_scale", mtl, ("g",), lambda lib: (_mt_coef(coef, mtl),))
 
 
 def mt_adamw(mtl: MultiTensorList, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
              coef: Optional[torch.Tensor] = None) -> None:
     """torch.optim.AdamW's step over the list (p, m, v updated in place from g; include/cvvae.h cvvae_mt_adamw), with the gradients
     read as coef g when coef (one fp32 DEVICE element) is given; the per-tensor step_size / bias2_sqrt come from MultiTensorList.set"""
-    lib, dt, chunks, table, n = _mt_args(mtl, ("g", "p", "m", "v"))
-    if mtl.step_size is None:
-        raise ValueError("MultiTensorList: step_size / bias2_sqrt were never set")
-    L.check(lib.cvvae_mt_adamw(dt, chunks, table, n, float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
-                               _mt_coef(coef, mtl) if coef is not None else None, _stream(mtl.table)), "cvvae_mt_adamw")
+    _mt_adamw("cvvae_mt_adamw", ("g", "p", "m", "v"), mtl, lr, beta1, beta2, eps, weight_decay, coef)
 
 
 def mt_adamw_master(mtl: MultiTensorList, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
@@ -1644,21 +1649,18 @@ def mt_adamw_master(mtl: MultiTensorList, lr: float, beta1: float, beta2: float,
     """mt_adamw for a list of 16-bit parameters on fp32 master weights (include/cvvae.h cvvae_mt_adamw_master): mtl.dtype (bf16 or
     fp16) is the type of g and p; m, v and the masters -- the list's `shadow` field -- are fp32.  Masters, m and v are updated as
     mt_adamw updates p, m and v, and p is rewritten as the new master rounded to nearest even, in the same pass"""
-    lib, dt, chunks, table, n = _mt_args(mtl, ("g", "p", "m", "v", "shadow"))
-    if mtl.step_size is None:
-        raise ValueError("MultiTensorList: step_size / bias2_sqrt were never set")
-    L.check(lib.cvvae_mt_adamw_master(dt, chunks, table, n, float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
-                                      _mt_coef(coef, mtl) if coef is not None else None, _stream(mtl.table)), "cvvae_mt_adamw_master")
+    _mt_adamw("cvvae_mt_adamw_master", ("g", "p", "m", "v", "shadow"), mtl, lr, beta1, beta2, eps, weight_decay, coef)
 
 
 def mt_sumsq(mtl: MultiTensorList, partials: torch.Tensor) -> None:
     """the first stage of mt_grad_norm for a list of any float dtype (include/cvvae.h cvvae_mt_sumsq): one fp32 partial per chunk into
     partials[0, n_chunks), an fp32 DEVICE tensor -- usually a slice of the workspace that the lists of one mixed-dtype norm share"""
-    lib, dt, chunks, table, n = _mt_args(mtl, ("g",))
-    if (partials.dtype != torch.float32 or partials.device != mtl.table.device or not partials.is_contiguous()
-            or partials.numel() < n):
-        raise ValueError("partials: a contiguous fp32 tensor on the list's device with an element per chunk")
-    L.check(lib.cvvae_mt_sumsq(dt, chunks, table, n, partials.data_ptr(), _stream(mtl.table)), "cvvae_mt_sumsq")
+    def args(lib):
+        if (partials.dtype != torch.float32 or partials.device != mtl.table.device or not partials.is_contiguous()
+                or partials.numel() < mtl.n_chunks):
+            raise ValueError("partials: a contiguous fp32 tensor on the list's device with an element per chunk")
+        return (partials,)
+    _mt_pass("cvvae_mt_sumsq", mtl, ("g",), args)
 
 
 def mt_norm_finish(partials: torch.Tensor, max_norm: float) -> torch.Tensor:
@@ -1676,12 +1678,10 @@ def mt_norm_finish(partials: torch.Tensor, max_norm: float) -> torch.Tensor:
 
 def mt_ema(mtl: MultiTensorList, one_minus_decay: float) -> None:
     """shadow <- shadow - one_minus_decay (shadow - p) over the list"""
-    lib, dt, chunks, table, n = _mt_args(mtl, ("p", "shadow"))
-    L.check(lib.cvvae_mt_ema(dt, chunks, table, n, float(one_minus_decay), _stream(mtl.table)), "cvvae_mt_ema")
+    _mt_pass("cvvae_mt_ema", mtl, ("p", "shadow"), lambda lib: (float(one_minus_decay),))
 
 
 def mt_pack(mtl: MultiTensorList, divisor: float) -> None:
     """shadow <- g / divisor over the list (include/cvvae.h cvvae_mt_pack): the gradients into their slots of the bucket that the
     data-parallel exchange all-reduces (cvvae_amd/ddp.py), zeros where the list's g entry is None.  A correctly rounded fp32 division"""
-    lib, dt, chunks, table, n = _mt_args(mtl, ("g", "shadow"))
-    L.check(lib.cvvae_mt_pack(dt, chunks, table, n, float(divisor), _stream(mtl.table)), "cvvae_mt_pack")
+    _mt_pass("cvvae_mt_pack", mtl, ("g", "shadow"), lambda lib: (float(divisor),))
