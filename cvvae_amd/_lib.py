@@ -186,11 +186,12 @@ PROTOTYPES = {
 _lib = None
 
 
-# translation units whose kernels only run in training (weight gradients, channel sums, their reductions) or in scoring a
-# reconstruction (metrics_kernels.hip), in logging one (panel_kernels.hip) or in making a batch (clip_kernels.hip): no launch of an
-# encode / decode step comes from them, so the counters of the inference bench do not go stale when they change
-TRAINING_ONLY_SOURCES = ("wgrad_kernel.hip", "loss_kernels.hip", "disc_kernels.hip", "optim_kernels.hip", "metrics_kernels.hip",
-                         "panel_kernels.hip", "clip_kernels.hip")
+# translation units whose kernels only run in training (weight gradients in wgrad_kernel.hip; every other backward pass -- the
+# GroupNorm, softmax and temporal-attention backward, channel sums, the padding and upsample adjoints -- in bwd_kernels.hip) or in
+# scoring a reconstruction (metrics_kernels.hip), in logging one (panel_kernels.hip) or in making a batch (clip_kernels.hip): no
+# launch of an encode / decode step comes from them, so the counters of the inference bench do not go stale when they change
+TRAINING_ONLY_SOURCES = ("wgrad_kernel.hip", "bwd_kernels.hip", "loss_kernels.hip", "disc_kernels.hip", "optim_kernels.hip",
+                         "metrics_kernels.hip", "panel_kernels.hip", "clip_kernels.hip")
 
 
 def source_fingerprint() -> str:

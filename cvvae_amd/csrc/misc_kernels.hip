@@ -1,5 +1,6 @@
-// misc_kernels.hip -- the HBM-bound kernels around the conv: GroupNorm statistics, LayerNorm, row softmax, transpose,
-// temporal attention, NCDHW<->NDHWC, tile blending (the weight packers are in pack_kernels.hip).  gfx950 only.
+// misc_kernels.hip -- the HBM-bound FORWARD kernels around the conv: GroupNorm statistics, LayerNorm, row softmax, transpose,
+// temporal attention, NCDHW<->NDHWC, tile blending (the weight packers are in pack_kernels.hip, the backward passes of these
+// kernels in bwd_kernels.hip: nothing here runs only in training).  gfx950 only.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -293,20 +294,6 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x,
 // ---------------------------------------------------------------------------------------------------------
 // row softmax: fp32 scores -> T probabilities; one block per row
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_reduce(float v, bool is_max, float* sh) {
-#pragma unroll
-  for (int off = 32; off; off >>= 1) {
-    const float o = __shfl_xor(v, off);
-    v = is_max ? fmaxf(v, o) : v + o;
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = sh[0];
-  for (int i = 1; i < (int)(blockDim.x >> 6); ++i) r = is_max ? fmaxf(r, sh[i]) : r + sh[i];
-  return r;
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restrict__ s, int n_valid, long long ld_s,
                                                            T* __restrict__ p, long long ld_p) {
@@ -321,286 +308,6 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
   sum = block_reduce(sum, false, sh);
   const float inv = 1.0f / sum;
   for (int i = threadIdx.x; i < (int)ld_p; i += 256) pr[i] = (T)(i < n_valid ? __expf(sr[i] - mx) * inv : 0.f);
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Input gradient of GroupNorm (+ SiLU) -- the frozen-module backward of the training path (cvvae_amd/grad.py).
-//   xh = (x - mean) * rstd = x * rs[c] + nm[c]      (rs = rstd, nm = -mean * rstd: cvvae_gn_finalize with gamma 1, beta 0)
-//   a  = xh * gamma[c] + beta[c],  y = act(a)       (the forward value the next conv consumed)
-//   gh = gy * act'(a) * gamma[c]                    (gradient w.r.t. xh)
-//   gx = rs * (gh - mean_grp(gh) - xh * mean_grp(gh * xh))  [+ add]
-// Pass 1 (gn_bwd_reduce_kernel) writes, per (row, pixel split, group), sum(gh) and sum(gh * xh); pass 2 (gn_bwd_apply_kernel) sums
-// the splits in index order (deterministic) and applies.  Channel quads never straddle a group (C / G a multiple of 4).
-// ---------------------------------------------------------------------------------------------------------
-struct GnBwdTab {  // the per-channel tables of my 8 channels
-  float rs[8], nm[8], ga[8], be[8];
-};
-__device__ __forceinline__ void gn_bwd_load_tab(GnBwdTab& t, const float* __restrict__ rs, const float* __restrict__ nm,
-                                                const float* __restrict__ gamma, const float* __restrict__ beta, long long row,
-                                                int C, int c0) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    t.rs[j] = rs[row * C + c0 + j];
-    t.nm[j] = nm[row * C + c0 + j];
-    t.ga[j] = gamma[c0 + j];
-    t.be[j] = beta[c0 + j];
-  }
-}
-
-// PARAMS: also the per-channel sums of the affine gradients  d beta = sum gy act'(a),  d gamma = sum gy act'(a) xh  (the kernel forms
-// gy act'(a) anyway: training the norm costs no extra pass over x and gy), one [C][2] table per (row, split) in `wsp`
-template <typename T, bool PARAMS = false, int SUB = 4>  // SUB: channels per group-sum slot, as in gn_partial_kernel
-__global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ gy, long long S, int C,
-                                                            int G, int nsplit, const float* __restrict__ rs,
-                                                            const float* __restrict__ nm, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, int silu, float* __restrict__ ws,
-                                                            float* __restrict__ wsp = nullptr) {
-  const int split = blockIdx.x, row = blockIdx.y, tid = threadIdx.x;
-  const int cv = C >> 3, ppp = 256 / cv;
-  const int myv = tid % cv, mypl = tid / cv;
-  const long long per = (S + nsplit - 1) / nsplit;
-  const long long p0 = (long long)split * per;
-  long long p1 = p0 + per;
-  if (p1 > S) p1 = S;
-  GnBwdTab t;
-  gn_bwd_load_tab(t, rs, nm, gamma, beta, row, C, myv * 8);
-  constexpr int NS = 8 / SUB;
-  float a1[NS], a2[NS];
-#pragma unroll
-  for (int h = 0; h < NS; ++h) a1[h] = a2[h] = 0.f;
-  float pb[PARAMS ? 8 : 1], pg[PARAMS ? 8 : 1];
-#pragma unroll
-  for (int j = 0; j < (PARAMS ? 8 : 1); ++j) pb[j] = pg[j] = 0.f;
-  const T* xb = x + (long long)row * S * C + myv * 8;
-  const T* gb = gy + (long long)row * S * C + myv * 8;
-  // four pixels per trip: their 16-byte loads are issued together (one pixel per trip was latency bound: ~2 TB/s on the
-  // million-pixel tensors of a training step); lanes past the end re-read pixel px with a zeroed gradient
-  constexpr int U = 4;
-  for (long long px = p0 + mypl; px < p1; px += U * ppp) {
-    float f[U][8], g[U][8];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const bool ok = px + u * ppp < p1;
-      const long long q = ok ? px + u * ppp : px;
-      ld8<T>(xb + q * C, f[u]);
-      ld8<T>(gb + q * C, g[u]);
-      if (!ok) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) g[u][j] = 0.f;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float xh = __builtin_fmaf(f[u][j], t.rs[j], t.nm[j]);
-        const float a = __builtin_fmaf(xh, t.ga[j], t.be[j]);
-        const float gact = g[u][j] * (silu ? silu_grad_f(a) : 1.0f);
-        const float gh = gact * t.ga[j];
-        a1[j / SUB] += gh;
-        a2[j / SUB] += gh * xh;
-        if constexpr (PARAMS) {
-          pb[j] += gact;
-          pg[j] += gact * xh;
-        }
-      }
-    }
-  }
-  if constexpr (PARAMS) {  // per channel: the pixel lanes of its vector, in index order
-    __shared__ float shp[256][17];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      shp[tid][j] = pb[j];
-      shp[tid][8 + j] = pg[j];
-    }
-    __syncthreads();
-    for (int c = tid; c < C; c += 256) {
-      float s1 = 0.f, s2 = 0.f;
-      for (int pl = 0; pl < ppp; ++pl) {
-        s1 += shp[pl * cv + (c >> 3)][c & 7];
-        s2 += shp[pl * cv + (c >> 3)][8 + (c & 7)];
-      }
-      float* o = wsp + (((long long)row * nsplit + split) * C + c) * 2;
-      o[0] = s1;
-      o[1] = s2;
-    }
-  }
-  __shared__ float sh1[256][NS], sh2[256][NS];
-#pragma unroll
-  for (int h = 0; h < NS; ++h) {
-    sh1[tid][h] = a1[h];
-    sh2[tid][h] = a2[h];
-  }
-  __syncthreads();
-  if (tid < G) {  // group tid: its channel slots (quads / pairs) q, every pixel lane, in index order
-    const int qpg = (C / G) / SUB;
-    float s1 = 0.f, s2 = 0.f;
-    for (int q = tid * qpg; q < (tid + 1) * qpg; ++q)
-      for (int pl = 0; pl < ppp; ++pl) {
-        const int th = pl * cv + q / NS;
-        s1 += sh1[th][q % NS];
-        s2 += sh2[th][q % NS];
-      }
-    float* o = ws + (((long long)row * nsplit + split) * G + tid) * 2;
-    o[0] = s1;
-    o[1] = s2;
-  }
-}
-
-template <typename T, int SUB = 4>
-__global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ gy,
-                                                           const T* __restrict__ add, T* __restrict__ out, long long S, int C, int G,
-                                                           int nsplit, const float* __restrict__ rs, const float* __restrict__ nm,
-                                                           const float* __restrict__ gamma, const float* __restrict__ beta, int silu,
-                                                           const float* __restrict__ ws) {
-  const int row = blockIdx.y, tid = threadIdx.x;
-  __shared__ float c1[64], c2[64], q1[256], q2[256];
-  {  // group g = tid % G, split lane l = tid / G sums splits l, l + lanes, ...; the lanes are then added in index order
-    const int lanes = 256 / G, g = tid % G, l = tid / G;
-    float s1 = 0.f, s2 = 0.f;
-    if (l < lanes)
-      for (int sp = l; sp < nsplit; sp += lanes) {
-        const float2 o = *reinterpret_cast<const float2*>(ws + (((long long)row * nsplit + sp) * G + g) * 2);
-        s1 += o.x;
-        s2 += o.y;
-      }
-    q1[tid] = s1;
-    q2[tid] = s2;
-    __syncthreads();
-    if (tid < G) {
-      s1 = 0.f; s2 = 0.f;
-      for (int k = 0; k < lanes; ++k) {
-        s1 += q1[k * G + tid];
-        s2 += q2[k * G + tid];
-      }
-      const float invd = 1.0f / ((float)(C / G) * (float)S);
-      c1[tid] = s1 * invd;
-      c2[tid] = s2 * invd;
-    }
-  }
-  __syncthreads();
-  const int cv = C >> 3;
-  const int myv = tid % cv;  // 256 % cv == 0 and the stride below is a multiple of 256: my channel vector is fixed
-  GnBwdTab t;
-  gn_bwd_load_tab(t, rs, nm, gamma, beta, row, C, myv * 8);
-  const int cpg = C / G;
-  constexpr int NS = 8 / SUB;
-  float m1[NS], m2[NS];  // the group means of my channel slots
-#pragma unroll
-  for (int h = 0; h < NS; ++h) {
-    m1[h] = c1[(myv * 8 + h * SUB) / cpg];
-    m2[h] = c2[(myv * 8 + h * SUB) / cpg];
-  }
-  const long long nvec = S * cv, base = (long long)row * S * C;
-  for (long long v = (long long)blockIdx.x * 256 + tid; v < nvec; v += (long long)gridDim.x * 256) {
-    const long long off = base + v * 8;  // v = pixel * cv + myv
-    float f[8], g[8], ad[8];
-    ld8<T>(x + off, f);
-    ld8<T>(gy + off, g);
-    if (add) ld8<T>(add + off, ad);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float xh = __builtin_fmaf(f[j], t.rs[j], t.nm[j]);
-      const float a = __builtin_fmaf(xh, t.ga[j], t.be[j]);
-      const float gh = g[j] * (silu ? silu_grad_f(a) : 1.0f) * t.ga[j];
-      const float r = t.rs[j] * (gh - m1[j / SUB] - xh * m2[j / SUB]);
-      f[j] = add ? r + ad[j] : r;
-    }
-    st8<T>(out + off, f);
-  }
-}
-
-// gradient of the row softmax: gs = alpha * p * (gp - sum_j p_j gp_j); columns >= n_valid (up to ld_o) are written as 0
-template <typename T>
-__global__ __launch_bounds__(256) void softmax_bwd_rows_kernel(const T* __restrict__ p, long long ld_p, const float* __restrict__ gp,
-                                                               long long ld_g, int n_valid, float alpha, T* __restrict__ out,
-                                                               long long ld_o) {
-  __shared__ float sh[4];
-  const T* pr = p + (long long)blockIdx.x * ld_p;
-  const float* gr = gp + (long long)blockIdx.x * ld_g;
-  T* orow = out + (long long)blockIdx.x * ld_o;
-  float dot = 0.f;
-  for (int i = threadIdx.x; i < n_valid; i += 256) dot += (float)pr[i] * gr[i];
-  dot = block_reduce(dot, false, sh);
-  for (int i = threadIdx.x; i < (int)ld_o; i += 256) orow[i] = (T)(i < n_valid ? alpha * (float)pr[i] * (gr[i] - dot) : 0.f);
-}
-
-// gradient of the nearest-neighbour x2 upsample (H and W): out[n][y][x][c] = sum of the 2x2 block of g [n][2H][2W][C]
-template <typename T>
-__global__ __launch_bounds__(256) void upsample2x_sum_kernel(const T* __restrict__ g, long long N, int H, int W, int C,
-                                                             T* __restrict__ out) {
-  const int cv = C >> 3;
-  const long long nvec = N * H * W * cv;
-  for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += (long long)gridDim.x * 256) {
-    const int c0 = (int)(v % cv) * 8;
-    long long pix = v / cv;
-    const int xo = (int)(pix % W);
-    pix /= W;
-    const int yo = (int)(pix % H);
-    const long long n = pix / H;
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      float f[8];
-      ld8<T>(g + (((n * 2 * H + 2 * yo + (d >> 1)) * 2 * W) + 2 * xo + (d & 1)) * C + c0, f);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] += f[j];
-    }
-    st8<T>(out + ((n * H + yo) * W + xo) * C + c0, acc);
-  }
-}
-
-static inline int gn_bwd_splits(long long S) {  // >= 512 pixels per split (a 147 k-pixel tensor at 2048 had 72 workgroups for 256 CUs)
-  // (up to 1024 splits: a 5-D GroupNorm has ONE row per sample, and 64 workgroups left three quarters of the CUs idle on the
-  //  million-pixel tensors of a training step -- 372 us per call, profiles/r4_train_step_kernel_stats_v2.txt)
-  const long long n = (S + 511) / 512;
-  return (int)(n < 1 ? 1 : (n > 1024 ? 1024 : n));
-}
-// sum1[c], sum2[c] = sums over `nparts` [C][2] tables (a block = 32 channels x 8 part lanes, parts summed in a fixed order)
-__global__ __launch_bounds__(256) void gn_params_final_kernel(const float* __restrict__ ws, int nparts, int C, float* __restrict__ o1,
-                                                              float* __restrict__ o2) {
-  __shared__ float sh[8][32][2];
-  const int cl = threadIdx.x & 31, pl = threadIdx.x >> 5;
-  const int c = blockIdx.x * 32 + cl;
-  float a1 = 0.f, a2 = 0.f;
-  if (c < C)
-    for (int i = pl; i < nparts; i += 8) {
-      const float2 v = *reinterpret_cast<const float2*>(ws + ((long long)i * C + c) * 2);
-      a1 += v.x;
-      a2 += v.y;
-    }
-  sh[pl][cl][0] = a1;
-  sh[pl][cl][1] = a2;
-  __syncthreads();
-  if (pl == 0 && c < C) {
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      s1 += sh[k][cl][0];
-      s2 += sh[k][cl][1];
-    }
-    o1[c] = s1;
-    o2[c] = s2;
-  }
-}
-
-template <typename T, int SUB = 4>
-static void gn_bwd_launch(const void* x, const void* gy, const void* add, int rows, long long S, int C, int G, const float* rs,
-                          const float* nm, const float* gamma, const float* beta, int silu, void* gx, float* ws, hipStream_t s,
-                          float* dgamma = nullptr, float* dbeta = nullptr) {
-  const int nsplit = gn_bwd_splits(S);
-  if (dgamma) {  // training the norm: the affine sums ride on the reduction pass (tables behind the group sums in the workspace)
-    float* wsp = ws + (long long)rows * nsplit * G * 2;
-    hipLaunchKernelGGL((gn_bwd_reduce_kernel<T, true, SUB>), dim3(nsplit, rows), dim3(256), 0, s, (const T*)x, (const T*)gy, S, C, G, nsplit,
-                       rs, nm, gamma, beta, silu, ws, wsp);
-    hipLaunchKernelGGL(gn_params_final_kernel, dim3((C + 31) / 32), dim3(256), 0, s, (const float*)wsp, rows * nsplit, C, dbeta, dgamma);
-  } else
-  hipLaunchKernelGGL((gn_bwd_reduce_kernel<T, false, SUB>), dim3(nsplit, rows), dim3(256), 0, s, (const T*)x, (const T*)gy, S, C, G, nsplit, rs, nm,
-                     gamma, beta, silu, ws);
-  long long blocks = (S * (C / 8) + 255) / 256;
-  if (blocks > 2048) blocks = 2048;  // grid-stride beyond 8 blocks per CU and row
-  hipLaunchKernelGGL((gn_bwd_apply_kernel<T, SUB>), dim3((unsigned)blocks, rows), dim3(256), 0, s, (const T*)x, (const T*)gy, (const T*)add,
-                     (T*)gx, S, C, G, nsplit, rs, nm, gamma, beta, silu, ws);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1093,81 +800,6 @@ int cvvae_gn_finalize_frames(const float* partials, int32_t rows, int32_t frames
     return CVVAE_EINVAL;
   hipLaunchKernelGGL(gn_finalize_slabs_kernel, dim3(groups, rows * frames), dim3(256), 0, (hipStream_t)stream, partials,
                      (long long)slabs, groups, C, eps, gamma, beta, scale, shift, frames);
-  return launch_status();
-}
-
-int64_t cvvae_gn_bwd_workspace_bytes(int32_t rows, int32_t groups, int64_t S) {
-  if (rows <= 0 || groups <= 0 || S <= 0) return 0;
-  return (int64_t)rows * gn_bwd_splits(S) * groups * 2 * (int64_t)sizeof(float);
-}
-
-int64_t cvvae_gn_bwd_params_workspace_bytes(int32_t rows, int32_t groups, int64_t S, int32_t C) {
-  if (rows <= 0 || groups <= 0 || S <= 0 || C <= 0) return 0;
-  return (int64_t)rows * gn_bwd_splits(S) * (groups + C) * 2 * (int64_t)sizeof(float);
-}
-
-// group sums on channel quads where the groups are made of them, on pairs otherwise (groups of 2 or 6 channels)
-#define GN_BWD_LAUNCH(T, DG, DB) \
-  do { \
-    if ((C / groups) % 4 == 0) \
-      gn_bwd_launch<T, 4>(x, gy, add, rows, S, C, groups, rstd, nmean, gamma, beta, silu, gx, (float*)workspace, s, DG, DB); \
-    else \
-      gn_bwd_launch<T, 2>(x, gy, add, rows, S, C, groups, rstd, nmean, gamma, beta, silu, gx, (float*)workspace, s, DG, DB); \
-  } while (0)
-
-int cvvae_gn_bwd_input_params(int32_t dtype, const void* x, const void* gy, const void* add, int32_t rows, int64_t S, int32_t C,
-                              int32_t groups, const float* rstd, const float* nmean, const float* gamma, const float* beta,
-                              int32_t silu, void* gx, float* dgamma, float* dbeta, void* workspace, void* stream) {
-  if (!x || !gy || !gx || !rstd || !nmean || !gamma || !beta || !workspace || !dgamma || !dbeta || rows <= 0 || S <= 0 || C <= 0)
-    return CVVAE_EINVAL;
-  if (groups <= 0 || groups > 64 || C % groups || (C / groups) % 2 || C % 8 || C > 2048 || 256 % (C / 8)) return CVVAE_EUNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  const bool ok = by_dtype(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    GN_BWD_LAUNCH(T, dgamma, dbeta);
-  });
-  if (!ok) return CVVAE_EINVAL;
-  return launch_status();
-}
-
-int cvvae_gn_bwd_input(int32_t dtype, const void* x, const void* gy, const void* add, int32_t rows, int64_t S, int32_t C,
-                       int32_t groups, const float* rstd, const float* nmean, const float* gamma, const float* beta, int32_t silu,
-                       void* gx, void* workspace, void* stream) {
-  if (!x || !gy || !gx || !rstd || !nmean || !gamma || !beta || !workspace || rows <= 0 || S <= 0 || C <= 0) return CVVAE_EINVAL;
-  // 8-channel vectors that tile a 256-thread block; channel quads (or pairs) inside one group
-  if (groups <= 0 || groups > 64 || C % groups || (C / groups) % 2 || C % 8 || C > 2048 || 256 % (C / 8)) return CVVAE_EUNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  const bool ok = by_dtype(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    GN_BWD_LAUNCH(T, nullptr, nullptr);
-  });
-  if (!ok) return CVVAE_EINVAL;
-  return launch_status();
-}
-
-int cvvae_softmax_bwd_rows(int32_t dtype, const void* p, int64_t ld_p, const float* gp, int64_t ld_g, int64_t rows, int32_t n_valid,
-                           float alpha, void* gs, int64_t ld_o, void* stream) {
-  if (!p || !gp || !gs || rows <= 0 || n_valid <= 0 || ld_p < n_valid || ld_g < n_valid || ld_o < n_valid) return CVVAE_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const bool ok = by_dtype(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    hipLaunchKernelGGL(softmax_bwd_rows_kernel<T>, dim3((unsigned)rows), dim3(256), 0, s, (const T*)p, (long long)ld_p, gp,
-                       (long long)ld_g, n_valid, alpha, (T*)gs, (long long)ld_o);
-  });
-  if (!ok) return CVVAE_EINVAL;
-  return launch_status();
-}
-
-int cvvae_upsample2x_sum(int32_t dtype, const void* g, int64_t N, int32_t H, int32_t W, int32_t C, void* out, void* stream) {
-  if (!g || !out || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8) return CVVAE_EINVAL;
-  long long blocks = ((long long)N * H * W * (C / 8) + 255) / 256;
-  if (blocks > 256LL * 64) blocks = 256LL * 64;
-  hipStream_t s = (hipStream_t)stream;
-  const bool ok = by_dtype(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    hipLaunchKernelGGL(upsample2x_sum_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, s, (const T*)g, (long long)N, H, W, C, (T*)out);
-  });
-  if (!ok) return CVVAE_EINVAL;
   return launch_status();
 }
 

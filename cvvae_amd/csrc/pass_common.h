@@ -1,7 +1,8 @@
 // pass_common.h -- what the element-wise and reduction passes share: 8-element vector access, the 256-thread workgroup sum, the
-// GroupNorm record and its merge, the SiLU derivative, and the host side's dtype dispatch.  gfx950 only.  One definition of each:
-// misc_kernels.hip and disc_kernels.hip must agree on WStat / chan_merge (cvvae_gn_finalize merges the records both write), and
-// a fix to a store's rounding or a merge's NaN handling belongs in one place.
+// softmax passes' row reduction, the GroupNorm record and its merge, the SiLU derivative, and the host side's dtype dispatch.
+// gfx950 only.  One definition of each: misc_kernels.hip and disc_kernels.hip must agree on WStat / chan_merge (cvvae_gn_finalize
+// merges the records both write), the forward passes of misc_kernels.hip and their adjoints in bwd_kernels.hip on ld8 / st8 and
+// the SiLU derivative, and a fix to a store's rounding or a merge's NaN handling belongs in one place.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -118,6 +119,22 @@ __device__ __forceinline__ float block_sum(float x) {
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
   __syncthreads();
   return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+// sum or maximum over a workgroup of whole waves, valid in every thread, through the caller's sh[waves]: the row reduction of the
+// softmax passes (misc_kernels.hip forward, bwd_kernels.hip backward)
+__device__ __forceinline__ float block_reduce(float v, bool is_max, float* sh) {
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    const float o = __shfl_xor(v, off);
+    v = is_max ? fmaxf(v, o) : v + o;
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float r = sh[0];
+  for (int i = 1; i < (int)(blockDim.x >> 6); ++i) r = is_max ? fmaxf(r, sh[i]) : r + sh[i];
+  return r;
 }
 
 // one GroupNorm record (count, mean, sum of squared deviations) and Chan's merge of two of them

@@ -1,5 +1,6 @@
-// wgrad_kernel.hip -- weight gradient of the codec's convolutions on MFMA, and the small reductions of the training-side backward
-// (bias / GroupNorm-affine gradients, the adjoint of replicate padding).  SURVEY.md 8(f) rank 4: training the 3-D networks
+// wgrad_kernel.hip -- weight gradient of the codec's convolutions on MFMA: wgrad_kernel, wgrad_dma_kernel, wgrad_reduce_kernel,
+// their launch plan and entry points, and nothing else (the other backward passes -- channel sums, the padding adjoint, the
+// temporal-attention backward -- are in bwd_kernels.hip).  SURVEY.md 8(f) rank 4: training the 3-D networks
 // (/root/reference/lvdm/models/autoencoder.py:1057-1090 runs `z, xrec = self(x)` through the TRAINABLE encoder / decoder).
 //
 //   dW[co][ci][tap] = sum over output pixels p of  gy[p][co] * a[src(p, tap)][ci]
@@ -765,323 +766,6 @@ static int wgrad_launch(const cvvae_conv_desc* d, const void* a, const void* gy,
   return d->sW == 2 ? wgrad_launch_sw<T, KHW, XP, 2>(d, a, gy, g_ps, dw, db, ws, s) : wgrad_launch_sw<T, KHW, XP, 1>(d, a, gy, g_ps, dw, db, ws, s);
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// per-channel sums over pixels: bias gradients (x = null: sum g) and GroupNorm affine gradients
-//   d beta[c] = sum g * act'(a),  d gamma[c] = sum g * act'(a) * xh      (xh, a as in gn_bwd_*: misc_kernels.hip)
-// Two passes: per (row, split) partial sums [C][2] written in place, then summed in index order.
-// ---------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void chan_sums_kernel(const T* __restrict__ x, const T* __restrict__ g, long long S, int C,
-                                                        long long g_ps, int nsplit, const float* __restrict__ rs,
-                                                        const float* __restrict__ nm, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, int silu, float* __restrict__ ws) {
-  const int split = blockIdx.x, row = blockIdx.y, tid = threadIdx.x;
-  const int cv = (C + 7) >> 3;
-  const int ppp = 256 / cv > 0 ? 256 / cv : 1;
-  const int myv = tid % cv, mypl = tid / cv;
-  const long long per = (S + nsplit - 1) / nsplit;
-  const long long p0 = (long long)split * per;
-  long long p1 = p0 + per;
-  if (p1 > S) p1 = S;
-  float s1[8], s2[8], trs[8], tnm[8], tga[8], tbe[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    s1[j] = s2[j] = 0.f;
-    const int c = myv * 8 + j;
-    const bool ok = x != nullptr && c < C;
-    trs[j] = ok ? rs[(long long)row * C + c] : 0.f;
-    tnm[j] = ok ? nm[(long long)row * C + c] : 0.f;
-    tga[j] = ok ? gamma[c] : 0.f;
-    tbe[j] = ok ? beta[c] : 0.f;
-  }
-  if (mypl < ppp && myv * 8 < C) {
-    // four pixels per trip: their 16-byte loads are issued together (one pixel per trip left ~4 MB in flight on the chip --
-    // latency bound at ~2 TB/s); lanes past the end re-read pixel px with a zeroed gradient
-    constexpr int U = 4;
-    for (long long px = p0 + mypl; px < p1; px += U * ppp) {
-      float f[U][8], gg[U][8];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const bool ok = px + u * ppp < p1;
-        const long long q = ok ? px + u * ppp : px;
-        ld8<T>(g + ((long long)row * S + q) * g_ps + myv * 8, gg[u]);
-        if (x != nullptr) ld8<T>(x + ((long long)row * S + q) * (long long)C + myv * 8, f[u]);
-        if (!ok) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) gg[u][j] = 0.f;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (x != nullptr) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float xh = __builtin_fmaf(f[u][j], trs[j], tnm[j]);
-            const float a = __builtin_fmaf(xh, tga[j], tbe[j]);
-            const float ga = gg[u][j] * (silu ? silu_grad_f(a) : 1.0f);
-            s1[j] += ga;
-            s2[j] += ga * xh;
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) s1[j] += gg[u][j];
-        }
-      }
-    }
-  }
-  __shared__ float sh[256][17];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    sh[tid][j] = s1[j];
-    sh[tid][8 + j] = s2[j];
-  }
-  __syncthreads();
-  for (int c = tid; c < C; c += 256) {  // channel c: its vector c/8, every pixel lane, in index order
-    float a1 = 0.f, a2 = 0.f;
-    for (int pl = 0; pl < ppp; ++pl) {
-      const int th = pl * cv + (c >> 3);
-      if (th < 256) {
-        a1 += sh[th][c & 7];
-        a2 += sh[th][8 + (c & 7)];
-      }
-    }
-    float* o = ws + (((long long)row * nsplit + split) * C + c) * 2;
-    o[0] = a1;
-    o[1] = a2;
-  }
-}
-
-__global__ __launch_bounds__(256) void chan_sums_final_kernel(const float* __restrict__ ws, int nparts, int C, float* __restrict__ o1,
-                                                              float* __restrict__ o2) {
-  // a block = 32 channels x 8 part lanes: lane pl sums parts pl, pl + 8, ... (coalesced 256-byte rows), then the 8 lanes are
-  // added in index order -- a fixed summation order, hence bit-reproducible
-  __shared__ float sh[8][32][2];
-  const int cl = threadIdx.x & 31, pl = threadIdx.x >> 5;
-  const int c = blockIdx.x * 32 + cl;
-  float a1 = 0.f, a2 = 0.f;
-  if (c < C) {
-    int i = pl;
-    for (; i + 24 < nparts; i += 32) {  // four loads in flight, added in index order
-      float2 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float2*>(ws + ((long long)(i + 8 * u) * C + c) * 2);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) { a1 += v[u].x; a2 += v[u].y; }
-    }
-    for (; i < nparts; i += 8) {
-      const float2 v = *reinterpret_cast<const float2*>(ws + ((long long)i * C + c) * 2);
-      a1 += v.x;
-      a2 += v.y;
-    }
-  }
-  sh[pl][cl][0] = a1;
-  sh[pl][cl][1] = a2;
-  __syncthreads();
-  if (pl == 0 && c < C) {
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      s1 += sh[k][cl][0];
-      s2 += sh[k][cl][1];
-    }
-    if (o1) o1[c] = s1;
-    if (o2) o2[c] = s2;
-  }
-}
-
-static inline int chan_sums_splits(long long S, int rows, int C) {
-  // ~32 pixels per thread (8 trips of 4): a workgroup covers 256 / (C / 8) pixels per step, so wide tensors take short splits
-  // (at a fixed 1024 pixels per split a 512-channel tensor gave each thread 256 dependent trips and a 147 k-pixel one 144
-  // workgroups for 256 CUs)
-  const int cv = (C + 7) >> 3;
-  const int ppp = 256 / cv > 0 ? 256 / cv : 1;
-  long long per = 32ll * ppp;
-  if (per < 128) per = 128;
-  long long n = (S + per - 1) / per;
-  const long long cap = rows > 0 ? (2048 + rows - 1) / rows : 2048;
-  if (n > cap) n = cap;
-  return (int)(n < 1 ? 1 : n);
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// adjoint of replicate / zero padding: gp [B][Tp][Hp][Wp][C] is the gradient w.r.t. the PADDED input (front pads pt, ph, pw);
-// out[b][t][y][x] = sum of gp over every padded position that the forward's coordinate map sends to (t, y, x)
-// (replicate: clamp -- border elements collect their whole pad region; zero: only the interior copy).  `add` is summed in.
-// ---------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void pad_fold_kernel(const T* __restrict__ gp, int B, int T_, int H, int W, int C, int Tp, int Hp,
-                                                       int Wp, int pt, int ph, int pw, int mode_t, int mode_hw,
-                                                       const T* __restrict__ add, T* __restrict__ out) {
-  const int cv = C >> 3;
-  const long long nvec = (long long)B * T_ * H * W * cv;
-  for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += (long long)gridDim.x * 256) {
-    const int c0 = (int)(v % cv) * 8;
-    long long pix = v / cv;
-    const int x = (int)(pix % W);
-    pix /= W;
-    const int y = (int)(pix % H);
-    pix /= H;
-    const int t = (int)(pix % T_);
-    const int b = (int)(pix / T_);
-    // padded index range [lo, hi] that maps to coordinate c of an axis of length L
-    auto range = [](int c, int L, int pf, int Lp, int mode, int& lo, int& hi) {
-      lo = hi = c + pf;
-      if (mode) {
-        if (c == 0) lo = 0;
-        if (c == L - 1) hi = Lp - 1;
-      }
-    };
-    int t0, t1, y0, y1, x0, x1;
-    range(t, T_, pt, Tp, mode_t, t0, t1);
-    range(y, H, ph, Hp, mode_hw, y0, y1);
-    range(x, W, pw, Wp, mode_hw, x0, x1);
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int tp = t0; tp <= t1; ++tp)
-      for (int yp = y0; yp <= y1; ++yp)
-        for (int xp = x0; xp <= x1; ++xp) {
-          float f[8];
-          ld8<T>(gp + ((((long long)b * Tp + tp) * Hp + yp) * Wp + xp) * C + c0, f);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) acc[j] += f[j];
-        }
-    const long long off = ((((long long)b * T_ + t) * H + y) * W + x) * C + c0;
-    if (add) {
-      float f[8];
-      ld8<T>(add + off, f);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] += f[j];
-    }
-    st8<T>(out + off, acc);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// backward of cvvae_temporal_attention (MemoryEfficientAttnVideoBlock.attention_t, models/vae_models.py:573-587): per pixel,
-// softmax(q k^T * scale) v over the Tn <= 8 frames of a clip.  One wave per pixel, as the forward: pass 1 over the channels forms
-// S = q k^T and dP = go v^T (two 8 x 8 tables per lane, reduced over the wave), the softmax and its gradient
-// dS = scale * P o (dP - rowsum(P o dP)) are per lane; pass 2 writes dq = dS k, dk = dS^T q, dv = P^T go.
-// ---------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void temporal_attn_bwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
-                                                                const T* __restrict__ v, const T* __restrict__ go, long long P,
-                                                                int Tn, long long S, int C, float scale, T* __restrict__ gq,
-                                                                T* __restrict__ gk, T* __restrict__ gv) {
-  const long long pix = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);  // over B*S
-  if (pix >= P) return;
-  const int lane = threadIdx.x & 63;
-  const int nv = C >> 3;
-  const long long b = pix / S, s = pix - b * S;
-  const long long base = (b * Tn * S + s) * C, tstride = S * C;
-  float sc[8][8], dp[8][8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) sc[i][j] = dp[i][j] = 0.f;
-  for (int vv = lane; vv < nv; vv += 64) {
-    float qf[8][8], gf[8][8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      if (i < Tn) {
-        ld8<T>(q + base + i * tstride + vv * 8, qf[i]);
-        ld8<T>(go + base + i * tstride + vv * 8, gf[i]);
-      }
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (j < Tn) {
-        float kf[8], vf[8];
-        ld8<T>(k + base + j * tstride + vv * 8, kf);
-        ld8<T>(v + base + j * tstride + vv * 8, vf);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          if (i < Tn) {
-            float d1 = 0.f, d2 = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              d1 += qf[i][e] * kf[e];
-              d2 += gf[i][e] * vf[e];
-            }
-            sc[i][j] += d1;
-            dp[i][j] += d2;
-          }
-      }
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float x = sc[i][j], y = dp[i][j];
-#pragma unroll
-      for (int off = 32; off; off >>= 1) {
-        x += __shfl_xor(x, off);
-        y += __shfl_xor(y, off);
-      }
-      sc[i][j] = x * scale;
-      dp[i][j] = y;
-    }
-  // P (as the forward computes it), then dS in place of dp
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-    if (i < Tn) {
-      float mx = -3.0e38f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (j < Tn) mx = fmaxf(mx, sc[i][j]);
-      float sum = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (j < Tn) {
-          sc[i][j] = __expf(sc[i][j] - mx);
-          sum += sc[i][j];
-        }
-      const float inv = 1.0f / sum;
-      float dot = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        sc[i][j] = (j < Tn) ? sc[i][j] * inv : 0.f;
-        dot += sc[i][j] * dp[i][j];
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) dp[i][j] = (j < Tn) ? scale * sc[i][j] * (dp[i][j] - dot) : 0.f;
-    }
-  for (int vv = lane; vv < nv; vv += 64) {
-    float qf[8][8], gf[8][8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      if (i < Tn) {
-        ld8<T>(q + base + i * tstride + vv * 8, qf[i]);
-        ld8<T>(go + base + i * tstride + vv * 8, gf[i]);
-      }
-    float dq[8][8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) dq[i][e] = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (j < Tn) {
-        float kf[8], dk[8], dv[8];
-        ld8<T>(k + base + j * tstride + vv * 8, kf);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) dk[e] = dv[e] = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          if (i < Tn) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              dq[i][e] += dp[i][j] * kf[e];
-              dk[e] += dp[i][j] * qf[i][e];
-              dv[e] += sc[i][j] * gf[i][e];
-            }
-          }
-        st8<T>(gk + base + j * tstride + vv * 8, dk);
-        st8<T>(gv + base + j * tstride + vv * 8, dv);
-      }
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      if (i < Tn) st8<T>(gq + base + i * tstride + vv * 8, dq[i]);
-  }
-}
-
 }  // namespace cvvae
 
 using namespace cvvae;
@@ -1127,71 +811,6 @@ int cvvae_conv_wgrad_bias(const cvvae_conv_desc* d, const void* a, const void* g
             : wgrad_launch<T, 1, false>(d, a, gy, gy_pix_stride, dw, dbias, workspace, stream);
   });
   return rc;
-}
-
-int64_t cvvae_channel_sums_workspace_bytes(int32_t rows, int64_t S, int32_t C) {
-  if (rows <= 0 || S <= 0 || C <= 0) return CVVAE_EINVAL;
-  return (int64_t)rows * chan_sums_splits(S, rows, C) * C * 2 * (int64_t)sizeof(float);
-}
-
-// x == NULL: sum1[c] = sum over rows x S pixels of g (a bias gradient); else the GroupNorm affine gradients
-// sum1 = d beta, sum2 = d gamma with (rstd, -mean*rstd) tables [rows][C] as in cvvae_gn_bwd_input
-int cvvae_channel_sums(int32_t dtype, const void* x, const void* g, int64_t g_pix_stride, int32_t rows, int64_t S, int32_t C,
-                       const float* rstd, const float* nmean, const float* gamma, const float* beta, int32_t silu, float* sum1,
-                       float* sum2, void* workspace, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!g || !sum1 || !workspace || rows <= 0 || S <= 0 || C <= 0 || C % 8 || C > 2048 || g_pix_stride < C || g_pix_stride % 8)
-    return CVVAE_EINVAL;
-  if (x && (!rstd || !nmean || !gamma || !beta || !sum2 || g_pix_stride != C)) return CVVAE_EINVAL;
-  if ((C >> 3) > 256) return CVVAE_EUNSUPPORTED;
-  const int nsplit = chan_sums_splits(S, rows, C);
-  float* ws = (float*)workspace;
-  const bool ok = by_dtype(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    hipLaunchKernelGGL(chan_sums_kernel<T>, dim3(nsplit, rows), dim3(256), 0, stream, (const T*)x, (const T*)g, S, C, g_pix_stride, nsplit,
-                       rstd, nmean, gamma, beta, silu, ws);
-  });
-  if (!ok) return CVVAE_EINVAL;
-  int rc = launch_status();
-  if (rc) return rc;
-  hipLaunchKernelGGL(chan_sums_final_kernel, dim3((C + 31) / 32), dim3(256), 0, stream, (const float*)ws, rows * nsplit, C, sum1,
-                     sum2);
-  return (int)hipGetLastError();
-}
-
-int cvvae_pad_fold(int32_t dtype, const void* gp, int32_t B, int32_t T, int32_t H, int32_t W, int32_t C, int32_t pad_t_front,
-                   int32_t pad_t_back, int32_t pad_h, int32_t pad_w, int32_t pad_mode_t, int32_t pad_mode_hw, const void* add, void* out,
-                   void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!gp || !out || B <= 0 || T <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8) return CVVAE_EINVAL;
-  if (pad_t_front < 0 || pad_t_back < 0 || pad_h < 0 || pad_w < 0) return CVVAE_EINVAL;
-  const int Tp = T + pad_t_front + pad_t_back, Hp = H + 2 * pad_h, Wp = W + 2 * pad_w;
-  long long blocks = ((long long)B * T * H * W * (C / 8) + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  const bool ok = by_dtype(dtype, [&](auto tag) {
-    using TY = typename decltype(tag)::type;  // (T is the frame count here)
-    hipLaunchKernelGGL(pad_fold_kernel<TY>, dim3((unsigned)blocks), dim3(256), 0, stream, (const TY*)gp, B, T, H, W, C, Tp, Hp, Wp,
-                       pad_t_front, pad_h, pad_w, pad_mode_t, pad_mode_hw, (const TY*)add, (TY*)out);
-  });
-  if (!ok) return CVVAE_EINVAL;
-  return (int)hipGetLastError();
-}
-
-int cvvae_temporal_attention_bwd(int32_t dtype, const void* q, const void* k, const void* v, const void* go, int32_t B, int32_t Tn,
-                                 int64_t S, int32_t C, void* gq, void* gk, void* gv, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!q || !k || !v || !go || !gq || !gk || !gv || B <= 0 || Tn <= 0 || S <= 0 || C <= 0 || C % 8) return CVVAE_EINVAL;
-  if (Tn > 8) return CVVAE_EUNSUPPORTED;  // (the windows of the reference's wrapper give T' <= 5; longer sequences: not built)
-  const long long P = (long long)B * S;
-  const float scale = 1.0f / sqrtf((float)C);
-  const unsigned grid = (unsigned)((P + 3) / 4);
-  const bool ok = by_dtype(dtype, [&](auto tag) {
-    using TY = typename decltype(tag)::type;
-    hipLaunchKernelGGL(temporal_attn_bwd_kernel<TY>, dim3(grid), dim3(256), 0, stream, (const TY*)q, (const TY*)k, (const TY*)v,
-                       (const TY*)go, P, Tn, (long long)S, C, scale, (TY*)gq, (TY*)gk, (TY*)gv);
-  });
-  if (!ok) return CVVAE_EINVAL;
-  return (int)hipGetLastError();
 }
 
 }  // extern "C"

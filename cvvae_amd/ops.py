@@ -543,6 +543,20 @@ def transpose(x: torch.Tensor, ncols: Optional[int] = None, ld_out: Optional[int
     return out
 
 
+def _gn_bwd_operands(x: torch.Tensor, gy: torch.Tensor, tabs: Tuple[torch.Tensor, torch.Tensor], per_frame: bool,
+                     add: Optional[torch.Tensor] = None):
+    """the operand checks the three GroupNorm-backward wrappers share -> rows, S, C and the two tables"""
+    _need_gpu(x)
+    assert x.dim() == 5 and x.is_contiguous() and gy.is_contiguous() and gy.shape == x.shape and gy.dtype == x.dtype
+    B, T, H, W, C = x.shape
+    rows, S = (B * T, H * W) if per_frame else (B, T * H * W)
+    rs, nm = tabs
+    assert rs.dtype == torch.float32 and tuple(rs.shape) == (rows, C) and rs.is_contiguous() and nm.is_contiguous()
+    if add is not None:
+        assert add.shape == x.shape and add.dtype == x.dtype and add.is_contiguous()
+    return rows, S, C, rs, nm
+
+
 def gn_bwd_input(x: torch.Tensor, gy: torch.Tensor, tabs: Tuple[torch.Tensor, torch.Tensor], gamma: torch.Tensor,
                  beta: torch.Tensor, silu: bool, add: Optional[torch.Tensor] = None, per_frame: bool = False,
                  groups: int = 32) -> torch.Tensor:
@@ -550,15 +564,8 @@ def gn_bwd_input(x: torch.Tensor, gy: torch.Tensor, tabs: Tuple[torch.Tensor, to
     tabs = (rstd, -mean*rstd) fp32 tables [rows, C] = gn_finalize / gn_stats with gamma 1, beta 0; gamma / beta fp32 [C].
     `add` is summed into the result (the skip branch of a residual block)."""
     lib = L.load()
-    _need_gpu(x)
-    assert x.dim() == 5 and x.is_contiguous() and gy.is_contiguous() and gy.shape == x.shape and gy.dtype == x.dtype
-    B, T, H, W, C = x.shape
-    rows, S = (B * T, H * W) if per_frame else (B, T * H * W)
-    rs, nm = tabs
-    assert rs.dtype == torch.float32 and tuple(rs.shape) == (rows, C) and tuple(nm.shape) == (rows, C)
-    assert rs.is_contiguous() and nm.is_contiguous() and gamma.dtype == torch.float32 and gamma.numel() == C and beta.numel() == C
-    if add is not None:
-        assert add.shape == x.shape and add.dtype == x.dtype and add.is_contiguous()
+    rows, S, C, rs, nm = _gn_bwd_operands(x, gy, tabs, per_frame, add)
+    assert tuple(nm.shape) == (rows, C) and gamma.dtype == torch.float32 and gamma.numel() == C and beta.numel() == C
     out = torch.empty_like(x)
     ws = torch.empty(max(int(lib.cvvae_gn_bwd_workspace_bytes(rows, groups, S)), 16), dtype=torch.uint8, device=x.device)
     L.check(lib.cvvae_gn_bwd_input(_dt(x.dtype), x.data_ptr(), gy.data_ptr(), add.data_ptr() if add is not None else None, rows, S, C,
@@ -572,14 +579,7 @@ def gn_bwd_input_params(x: torch.Tensor, gy: torch.Tensor, tabs: Tuple[torch.Ten
                         groups: int = 32) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """gn_bwd_input for a trainable norm: (dL/dx, d gamma, d beta) in one reduction + one apply pass (cvvae_gn_bwd_input_params)"""
     lib = L.load()
-    _need_gpu(x)
-    assert x.dim() == 5 and x.is_contiguous() and gy.is_contiguous() and gy.shape == x.shape and gy.dtype == x.dtype
-    B, T, H, W, C = x.shape
-    rows, S = (B * T, H * W) if per_frame else (B, T * H * W)
-    rs, nm = tabs
-    assert rs.dtype == torch.float32 and tuple(rs.shape) == (rows, C) and rs.is_contiguous() and nm.is_contiguous()
-    if add is not None:
-        assert add.shape == x.shape and add.dtype == x.dtype and add.is_contiguous()
+    rows, S, C, rs, nm = _gn_bwd_operands(x, gy, tabs, per_frame, add)
     if C % groups or (C // groups) % 2 or C % 8 or C > 2048 or 256 % (C // 8):
         # (both GroupNorm backward kernels map a 256-thread block onto whole rows of 8-channel lanes; the model classes admit only
         #  widths of 128 * 2^k -- modeling._channel_constraints -- so this is a caller error, reported before the launch)
@@ -665,12 +665,7 @@ def gn_bwd_params(x: torch.Tensor, gy: torch.Tensor, tabs: Tuple[torch.Tensor, t
     """(d gamma, d beta) fp32 [C] of act(GroupNorm(x)) given gy = dL/d(act(...)): the affine half of
     aten::native_group_norm_backward (cvvae_channel_sums); arguments as gn_bwd_input."""
     lib = L.load()
-    _need_gpu(x)
-    assert x.dim() == 5 and x.is_contiguous() and gy.is_contiguous() and gy.shape == x.shape and gy.dtype == x.dtype
-    B, T, H, W, C = x.shape
-    rows, S = (B * T, H * W) if per_frame else (B, T * H * W)
-    rs, nm = tabs
-    assert rs.dtype == torch.float32 and tuple(rs.shape) == (rows, C) and rs.is_contiguous() and nm.is_contiguous()
+    rows, S, C, rs, nm = _gn_bwd_operands(x, gy, tabs, per_frame)
     ws = torch.empty(max(int(lib.cvvae_channel_sums_workspace_bytes(rows, S, C)), 16), dtype=torch.uint8, device=x.device)
     db = torch.empty(C, dtype=torch.float32, device=x.device)
     dg = torch.empty(C, dtype=torch.float32, device=x.device)

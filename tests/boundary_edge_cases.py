@@ -1,7 +1,7 @@
 """Case table of the network-boundary edge tests (a plain module, imported by tests/test_boundary_edges_host.py and
-tests/test_gpu_boundary_edges.py): the ten passes of cvvae_amd/csrc/misc_kernels.hip through which every tensor enters and leaves the
-networks -- the two layout moves, the two row-packers, the uint8 pixel conversions, the uint8 resize, the last layer's gather, the
-tile blend and the 2x2 sum.
+tests/test_gpu_boundary_edges.py): the ten passes through which every tensor enters and leaves the networks -- the two layout moves,
+the two row-packers, the uint8 pixel conversions, the uint8 resize, the last layer's gather and the tile blend of
+cvvae_amd/csrc/misc_kernels.hip, and the 2x2 sum of cvvae_amd/csrc/bwd_kernels.hip.
 
 A case is data only (the Case of tests/pass_edge_cases.py): a name, the op, the shape parameters, the dtypes it runs in, the name of
 its input recipe (tests/boundary_ref.py builds the tensors from it) and a seed.  A dtype of the converting moves is a pair

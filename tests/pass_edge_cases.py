@@ -4,7 +4,7 @@ temporal-attention kernels and their backward, the fused 512-channel attention a
 
 A case is data only: a name, the op, the shape parameters `p`, the dtypes it runs in, the name of its input recipe
 (tests/pass_ref.py builds the tensors from it) and a seed.  The shapes are the smallest that reach each edge of the kernels in
-cvvae_amd/csrc/misc_kernels.hip, attention_kernel.hip and wgrad_kernel.hip; the comment next to each group names the edge."""
+cvvae_amd/csrc/misc_kernels.hip, attention_kernel.hip and bwd_kernels.hip; the comment next to each group names the edge."""
 from dataclasses import dataclass, field
 from typing import Dict, List, Tuple
 

@@ -1,5 +1,6 @@
 """The passes at the networks' boundary, bit for bit at their edges (needs the MI355X): the layout moves, the row-packers, the uint8
-pixel conversions, the uint8 resize, the last layer's gather, the tile blend and the 2x2 sum of cvvae_amd/csrc/misc_kernels.hip.
+pixel conversions, the uint8 resize, the last layer's gather and the tile blend of cvvae_amd/csrc/misc_kernels.hip, and the 2x2 sum
+of cvvae_amd/csrc/bwd_kernels.hip.
 
 Every case of tests/boundary_edge_cases.py runs on the HIP kernels in each of its dtypes, twice on the same inputs: the two results
 must be bit-identical, and the first is held PER ELEMENT to the reference of tests/boundary_ref.py -- equality of the bits for the

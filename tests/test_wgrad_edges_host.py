@@ -57,7 +57,7 @@ def test_tables_cover_the_loop_edges():
     reg16 = [c for c in CONV if c.kernel == WC.REG and not c.xp]
     assert {c.out_grid[2] for c in reg16} >= {1, 127, 128, 129} and any(c.pmin >= 5 and c.out_grid[2] % 128 for c in reg16)
     assert all(BY_NAME[n].k[1] == 3 and WC.BF16 in BY_NAME[n].dtypes for n in WC.REG16_K3_CHILD) and len(WC.REG16_K3_CHILD) == 4
-    # chan_sums_kernel / chan_sums_final_kernel
+    # chan_sums_kernel / chan_sums_final_kernel (csrc/bwd_kernels.hip)
     for op in ("bias", "gn"):
         assert {c.C for c in CHAN if c.op == op} == {8, 24, 512, 2048}
     for C in (8, 24, 512, 2048):

@@ -1,7 +1,7 @@
 """Case tables of the weight-gradient edge tests (a plain module, imported by tests/test_wgrad_edges_host.py and
 tests/test_gpu_wgrad_edges.py): cvvae_conv_wgrad / cvvae_conv_wgrad_bias on all three of its kernels, the per-channel sums
-(ops.bias_grad, ops.gn_bwd_params) and the padding adjoint (ops.pad_fold) -- everything in cvvae_amd/csrc/wgrad_kernel.hip but the
-temporal-attention backward, which tests/pass_edge_cases.py covers.
+(ops.bias_grad, ops.gn_bwd_params) and the padding adjoint (ops.pad_fold) -- everything in cvvae_amd/csrc/wgrad_kernel.hip, and of
+cvvae_amd/csrc/bwd_kernels.hip what tests/pass_edge_cases.py and tests/boundary_edge_cases.py do not cover.
 
 A case is data only.  A conv case names the edge it reaches and DECLARES the facts of the launch plan it depends on: the kernel,
 the slab count, the fewest and most K panels a slab multiplies, how many slabs start in the middle of an output row, which
