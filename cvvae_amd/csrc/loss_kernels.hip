@@ -1,16 +1,11 @@
 // loss_kernels.hip -- the passes of the training loss around the networks (cvvae_amd/loss.py): a deterministic map-reduce to one
-// fp32 scalar (pixel terms, KL, the GAN terms, the gradient norms of the adaptive weight), its adjoint, the same pair with a
-// frame-mapped second operand (the "random" / "mean" 2-D targets of the constraint losses), and the diagonal-Gaussian
-// posterior (sample + KL) forward and backward.  gfx950 only.  All of them are HBM- or latency-bound: plain C++.
-//
-// Order of summation.  Elements are numbered by their LOGICAL index i (outer dimensions slowest, the inner run fastest).  Group
-// g = elements [8g, 8g + 8) belongs to thread g % 256 of tile g / 256; workgroup w walks tiles w, w + grid, ...; a thread adds
-// its groups serially (each group's 8 terms first, in index order), the 64 lanes of a wave are merged by a butterfly, the four
-// waves through LDS in wave order, and stage 2 (one workgroup) merges the per-workgroup partials the same way.  The grid is a
-// function of the element count alone and nothing is atomic, so the sum is a function of the logical values alone: the same
-// inputs give the same bits on every run, and so do a strided view and its contiguous copy, at any alignment.
-// A group is read with 16-byte loads when it lies inside one inner run and its address is 16-byte aligned, element by element
-// otherwise (the head and tail of a run whose length or base is not a multiple of 8 elements).
+// fp32 scalar (pixel terms, KL, the GAN terms, the gradient norms of the adaptive weight) and its adjoint, over two operand
+// sources -- a strided view, a contiguous run, or the frame-mapped clip of the constraint losses' "random" / "mean" 2-D targets --
+// and the diagonal-Gaussian posterior (sample + KL) forward and backward.  gfx950 only.  All of them are HBM- or latency-bound:
+// plain C++.  Every kernel numbers its elements by their LOGICAL index and visits them through walk(), which fixes the order of
+// summation; a source only says where the value of a logical index lives, so the sum is a function of the logical values alone:
+// the same inputs give the same bits on every run, and so do a strided view and its contiguous copy at any alignment, and a
+// frame-mapped clip and its materialised target.
 #include "pass_common.h"
 
 namespace cvvae {
@@ -20,6 +15,40 @@ constexpr int WG = 256;              // threads per workgroup
 constexpr int VEC = 8;               // elements per group
 constexpr int TILE = WG * VEC;       // elements per workgroup pass
 constexpr int MAX_BLOCKS = 2048;     // stage-1 grid cap = stage-2's serial depth x 256
+constexpr int MAX_BLOCKS_BWD = 65536;  // the adjoints' grid cap (nothing reads their grid back)
+
+// Order of summation.  Elements are numbered by their logical index i (outer dimensions slowest, the inner run fastest).  Group
+// g = elements [8g, 8g + 8) belongs to thread g % 256 of tile g / 256; workgroup w walks tiles w, w + grid, ...; the last group
+// may hold n < 8 elements.  walk() calls f(i, n) for each group of the calling thread, in that order.  A reducing kernel adds a
+// group's 8 terms first, in index order, and its groups serially; block_sum merges the 64 lanes of a wave by a butterfly and the
+// four waves through LDS in wave order, and stage 2 (reduce_final_kernel, one workgroup) merges the per-workgroup partials the
+// same way.  The grid is a function of the element count alone and nothing is atomic.  (The kernels' lambdas are always_inline:
+// inlined together with walk, before any optimisation, they compile as the loop bodies they are; left to the inliner's own time
+// the fp32 instantiations held up to 10 more VGPRs.)
+template <typename F>
+__device__ __forceinline__ void walk(long long total, F&& f) {
+  const long long ntiles = (total + TILE - 1) / TILE;
+  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const long long i = (t * WG + threadIdx.x) * VEC;
+    if (i >= total) continue;
+    f(i, (total - i) < VEC ? (int)(total - i) : VEC);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Operand sources: load(i, n, f) puts the n (<= 8) values of logical indices [i, i + n) into f (the rest of f is zero or unused).
+// A group is read with 16-byte loads when it lies inside one inner run and its address is 16-byte aligned, element by element
+// otherwise (the head and tail of a run whose length or base is not a multiple of 8 elements).  GRAD: the operand can take the
+// adjoint's gradient, contiguous over the logical index.
+// ---------------------------------------------------------------------------------------------------------
+// a contiguous run
+template <typename T>
+struct Run {
+  using type = T;
+  static constexpr bool GRAD = true;
+  const T* p;
+  __device__ __forceinline__ void load(long long i, int n, float (&f)[VEC]) const { ld8_n<T>(p + i, n, f); }
+};
 
 // up to three outer dimensions (slowest first) with one operand's element strides, and the inner run
 struct View {
@@ -30,23 +59,92 @@ struct View {
   }
 };
 
-// the n (<= 8) elements of logical indices [i, i + n) of a strided operand
-template <typename T>
-__device__ __forceinline__ void gather8(const T* p, const View& v, long long i, int n, float (&f)[VEC]) {
-  const long long row = i / v.L, j = i - row * v.L;
-  if (n == VEC && j + VEC <= v.L) {
-    ld8_n<T>(p + v.offset(row, j), VEC, f);
-    return;
-  }
+// a strided view; OPTIONAL: a null p is an absent operand, which reads as zeros
+template <typename T, bool OPTIONAL = false>
+struct Strided {
+  using type = T;
+  static constexpr bool GRAD = true;
+  const T* p;
+  View v;
+  __device__ __forceinline__ void load(long long i, int n, float (&f)[VEC]) const {
+    if (OPTIONAL && !p) {
 #pragma unroll
-  for (int k = 0; k < VEC; ++k) {
-    f[k] = 0.f;
-    if (k < n) {
-      const long long r = (i + k) / v.L;
-      f[k] = (float)p[v.offset(r, (i + k) - r * v.L)];
+      for (int k = 0; k < VEC; ++k) f[k] = 0.f;
+      return;
+    }
+    const long long row = i / v.L, j = i - row * v.L;
+    if (n == VEC && j + VEC <= v.L) {
+      ld8_n<T>(p + v.offset(row, j), VEC, f);
+      return;
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      f[k] = 0.f;
+      if (k < n) {
+        const long long r = (i + k) / v.L;
+        f[k] = (float)p[v.offset(r, (i + k) - r * v.L)];
+      }
     }
   }
-}
+};
+
+// a frame-mapped clip (cvvae_frame_map): the 2-D target of the constraint losses, rows x frames_out x HW, whose frame t' is a frame
+// of the clip picked through a table (GATHER) or the mean of `group` consecutive frames (GROUP_MEAN) -- read from the clip in
+// place.  The table travels in the kernel arguments (of the kernels over this source only).
+struct FrameMap {
+  int mode, group;
+  long long frames_out, HW, row_stride, frame_stride;
+  float inv_group;
+  int index[CVVAE_FMAP_MAX_FRAMES];
+};
+
+template <typename T>
+struct Frames {
+  using type = T;
+  static constexpr bool GRAD = false;
+  const T* clip;
+  FrameMap m;
+  // the n (<= 8) target values at position j of frame tf of row r, which lie inside that frame's run
+  __device__ __forceinline__ void run(long long r, long long tf, long long j, int n, float (&f)[VEC]) const {
+    const T* base = clip + r * m.row_stride + j;
+    if (m.mode == CVVAE_FMAP_GATHER) {
+      ld8_n<T>(base + (long long)m.index[tf] * m.frame_stride, n, f);
+      return;
+    }
+    if (tf == 0) {
+      ld8_n<T>(base, n, f);
+      return;
+    }
+    const long long s = 1 + (tf - 1) * m.group;
+    ld8_n<T>(base + s * m.frame_stride, n, f);
+    for (int q = 1; q < m.group; ++q) {
+      float c[VEC];
+      ld8_n<T>(base + (s + q) * m.frame_stride, n, c);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) f[k] += c[k];
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) f[k] = __fmul_rn(f[k], m.inv_group);  // (its own rounding: never contracted into the term's a - b)
+  }
+  __device__ __forceinline__ void load(long long i, int n, float (&f)[VEC]) const {
+    const long long fr = i / m.HW, j = i - fr * m.HW;
+    if (n == VEC && j + VEC <= m.HW) {
+      const long long r = fr / m.frames_out;
+      run(r, fr - r * m.frames_out, j, VEC, f);
+      return;
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      f[k] = 0.f;
+      if (k < n) {
+        const long long fk = (i + k) / m.HW, r = fk / m.frames_out;
+        float one[VEC];
+        run(r, fk - r * m.frames_out, (i + k) - fk * m.HW, 1, one);
+        f[k] = one[0];
+      }
+    }
+  }
+};
 
 // aten::softplus (beta 1, threshold 20) and its derivative
 __device__ __forceinline__ float softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }
@@ -83,28 +181,19 @@ __device__ __forceinline__ float term_grad(int op, float a, float b) {
   }
 }
 
-template <typename TA, typename TB>
-__global__ __launch_bounds__(WG) void reduce_partial_kernel(int op, const TA* __restrict__ a, View va, const TB* __restrict__ b,
-                                                            View vb, long long total, float* __restrict__ ws) {
-  const long long ntiles = (total + TILE - 1) / TILE;
+// stage 1: ws[workgroup] = the workgroup's sum of f_op(a, b)
+template <typename SA, typename SB>
+__global__ __launch_bounds__(WG) void reduce_partial_kernel(int op, const SA a, const SB b, long long total, float* __restrict__ ws) {
   float acc = 0.f;
-  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const long long i = (t * WG + threadIdx.x) * VEC;
-    if (i >= total) continue;
-    const int n = (total - i) < VEC ? (int)(total - i) : VEC;
+  walk(total, [&](long long i, int n) __attribute__((always_inline)) {
     float fa[VEC], fb[VEC];
-    gather8<TA>(a, va, i, n, fa);
-    if (b) {
-      gather8<TB>(b, vb, i, n, fb);
-    } else {
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) fb[k] = 0.f;
-    }
+    a.load(i, n, fa);
+    b.load(i, n, fb);
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < VEC; ++k) s += (k < n) ? term(op, fa[k], fb[k]) : 0.f;
     acc += s;
-  }
+  });
   acc = block_sum(acc);
   if (threadIdx.x == 0) ws[blockIdx.x] = acc;
 }
@@ -117,132 +206,24 @@ __global__ __launch_bounds__(WG) void reduce_final_kernel(const float* __restric
   if (threadIdx.x == 0) out[0] = scale * acc;
 }
 
-template <typename TA, typename TB>
-__global__ __launch_bounds__(WG) void reduce_bwd_kernel(int op, const TA* __restrict__ a, View va, const TB* __restrict__ b, View vb,
-                                                        long long total, const float* __restrict__ coef_dev, TA* __restrict__ ga,
-                                                        TB* __restrict__ gb) {
+// adjoint: ga = coef f_op'(a, b) and gb = -ga, each where asked for (gb: where b's source can take one)
+template <typename SA, typename SB>
+__global__ __launch_bounds__(WG) void reduce_bwd_kernel(int op, const SA a, const SB b, long long total, const float* __restrict__ coef_dev,
+                                                        typename SA::type* __restrict__ ga, typename SB::type* __restrict__ gb) {
   const float coef = coef_dev[0];
-  const long long ntiles = (total + TILE - 1) / TILE;
-  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const long long i = (t * WG + threadIdx.x) * VEC;
-    if (i >= total) continue;
-    const int n = (total - i) < VEC ? (int)(total - i) : VEC;
+  walk(total, [&](long long i, int n) __attribute__((always_inline)) {
     float fa[VEC], fb[VEC], g[VEC];
-    gather8<TA>(a, va, i, n, fa);
-    if (b) {
-      gather8<TB>(b, vb, i, n, fb);
-    } else {
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) fb[k] = 0.f;
-    }
+    a.load(i, n, fa);
+    b.load(i, n, fb);
 #pragma unroll
     for (int k = 0; k < VEC; ++k) g[k] = coef * term_grad(op, fa[k], fb[k]);
-    if (ga) st8_n<TA>(ga + i, g, n);
-    if (gb) {
+    if (ga) st8_n<typename SA::type>(ga + i, g, n);
+    if (SB::GRAD && gb) {
 #pragma unroll
       for (int k = 0; k < VEC; ++k) g[k] = -g[k];
-      st8_n<TB>(gb + i, g, n);
+      st8_n<typename SB::type>(gb + i, g, n);
     }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Frame-mapped second operand (cvvae_frame_map): the 2-D target of the constraint losses, rows x frames_out x HW, whose frame t'
-// is a frame of the clip picked through a table (GATHER) or the mean of `group` consecutive frames (GROUP_MEAN) -- read from the
-// clip in place.  The table travels in the kernel arguments.  Same element numbering, grid and two stages as above, so the sum
-// carries the bits of cvvae_reduce_sum over the materialised target.
-// ---------------------------------------------------------------------------------------------------------
-struct FrameMap {
-  int mode, group;
-  long long frames_out, HW, row_stride, frame_stride;
-  float inv_group;
-  int index[CVVAE_FMAP_MAX_FRAMES];
-};
-
-// the n (<= 8) target values at position j of frame tf of row r; whole = the group lies inside this frame's run
-template <typename T>
-__device__ __forceinline__ void target_run(const T* __restrict__ clip, const FrameMap& m, long long r, long long tf, long long j, int n,
-                                           float (&f)[VEC]) {
-  const T* base = clip + r * m.row_stride + j;
-  if (m.mode == CVVAE_FMAP_GATHER) {
-    ld8_n<T>(base + (long long)m.index[tf] * m.frame_stride, n, f);
-    return;
-  }
-  if (tf == 0) {
-    ld8_n<T>(base, n, f);
-    return;
-  }
-  const long long s = 1 + (tf - 1) * m.group;
-  ld8_n<T>(base + s * m.frame_stride, n, f);
-  for (int q = 1; q < m.group; ++q) {
-    float c[VEC];
-    ld8_n<T>(base + (s + q) * m.frame_stride, n, c);
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) f[k] += c[k];
-  }
-#pragma unroll
-  for (int k = 0; k < VEC; ++k) f[k] = __fmul_rn(f[k], m.inv_group);  // (its own rounding: never contracted into the term's a - b)
-}
-
-// the target values of logical indices [i, i + n)
-template <typename T>
-__device__ __forceinline__ void target8(const T* __restrict__ clip, const FrameMap& m, long long i, int n, float (&f)[VEC]) {
-  const long long fr = i / m.HW, j = i - fr * m.HW;
-  if (n == VEC && j + VEC <= m.HW) {
-    const long long r = fr / m.frames_out;
-    target_run<T>(clip, m, r, fr - r * m.frames_out, j, VEC, f);
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < VEC; ++k) {
-    f[k] = 0.f;
-    if (k < n) {
-      const long long fk = (i + k) / m.HW, r = fk / m.frames_out;
-      float one[VEC];
-      target_run<T>(clip, m, r, fk - r * m.frames_out, (i + k) - fk * m.HW, 1, one);
-      f[k] = one[0];
-    }
-  }
-}
-
-template <typename TA, typename TB>
-__global__ __launch_bounds__(WG) void reduce_frames_partial_kernel(int op, const TA* __restrict__ a, const TB* __restrict__ clip,
-                                                                   const FrameMap m, long long total, float* __restrict__ ws) {
-  const long long ntiles = (total + TILE - 1) / TILE;
-  float acc = 0.f;
-  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const long long i = (t * WG + threadIdx.x) * VEC;
-    if (i >= total) continue;
-    const int n = (total - i) < VEC ? (int)(total - i) : VEC;
-    float fa[VEC], fb[VEC];
-    ld8_n<TA>(a + i, n, fa);
-    target8<TB>(clip, m, i, n, fb);
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) s += (k < n) ? term(op, fa[k], fb[k]) : 0.f;
-    acc += s;
-  }
-  acc = block_sum(acc);
-  if (threadIdx.x == 0) ws[blockIdx.x] = acc;
-}
-
-template <typename TA, typename TB>
-__global__ __launch_bounds__(WG) void reduce_frames_bwd_kernel(int op, const TA* __restrict__ a, const TB* __restrict__ clip,
-                                                               const FrameMap m, long long total, const float* __restrict__ coef_dev,
-                                                               TA* __restrict__ ga) {
-  const float coef = coef_dev[0];
-  const long long ntiles = (total + TILE - 1) / TILE;
-  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const long long i = (t * WG + threadIdx.x) * VEC;
-    if (i >= total) continue;
-    const int n = (total - i) < VEC ? (int)(total - i) : VEC;
-    float fa[VEC], fb[VEC], g[VEC];
-    ld8_n<TA>(a + i, n, fa);
-    target8<TB>(clip, m, i, n, fb);
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) g[k] = coef * term_grad(op, fa[k], fb[k]);
-    st8_n<TA>(ga + i, g, n);
-  }
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -256,16 +237,13 @@ template <typename T>
 __global__ __launch_bounds__(WG) void gauss_reg_kernel(const T* __restrict__ mom, const T* __restrict__ noise, T* __restrict__ z,
                                                        long long CS, long long total, float* __restrict__ ws) {
   const View vm{1, 1 << 30, CS, 0, 0, 2 * CS};  // row b of the mean chunk starts at b * 2CS (n2 only has to exceed B)
-  const long long ntiles = (total + TILE - 1) / TILE;
+  const Strided<T> mean{mom, vm}, logvar{mom + CS, vm};
   float acc = 0.f;
-  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const long long i = (t * WG + threadIdx.x) * VEC;
-    if (i >= total) continue;
-    const int n = (total - i) < VEC ? (int)(total - i) : VEC;
+  walk(total, [&](long long i, int n) __attribute__((always_inline)) {
     float m[VEC], lv[VEC], e[VEC], o[VEC];
-    gather8<T>(mom, vm, i, n, m);
-    gather8<T>(mom + CS, vm, i, n, lv);
-    if (noise) ld8_n<T>(noise + i, n, e);
+    mean.load(i, n, m);
+    logvar.load(i, n, lv);
+    if (noise) Run<T>{noise}.load(i, n, e);
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
@@ -275,7 +253,7 @@ __global__ __launch_bounds__(WG) void gauss_reg_kernel(const T* __restrict__ mom
     }
     st8_n<T>(z + i, o, n);
     acc += s;
-  }
+  });
   acc = block_sum(acc);
   if (threadIdx.x == 0) ws[blockIdx.x] = acc;
 }
@@ -287,19 +265,16 @@ __global__ __launch_bounds__(WG) void gauss_reg_bwd_kernel(const T* __restrict__
                                                            T* __restrict__ gmom, long long CS, long long total) {
   const float coef = coef_dev[0];
   const View vm{1, 1 << 30, CS, 0, 0, 2 * CS};
-  const long long ntiles = (total + TILE - 1) / TILE;
-  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const long long i = (t * WG + threadIdx.x) * VEC;
-    if (i >= total) continue;
-    const int n = (total - i) < VEC ? (int)(total - i) : VEC;
+  const Strided<T> mean{mom, vm}, logvar{mom + CS, vm};
+  walk(total, [&](long long i, int n) __attribute__((always_inline)) {
     float m[VEC], lv[VEC], e[VEC], g[VEC], dm[VEC], dl[VEC];
-    gather8<T>(mom, vm, i, n, m);
-    gather8<T>(mom + CS, vm, i, n, lv);
+    mean.load(i, n, m);
+    logvar.load(i, n, lv);
 #pragma unroll
     for (int k = 0; k < VEC; ++k) e[k] = g[k] = 0.f;
     if (gz) {
-      ld8_n<T>(gz + i, n, g);
-      if (noise) ld8_n<T>(noise + i, n, e);
+      Run<T>{gz}.load(i, n, g);
+      if (noise) Run<T>{noise}.load(i, n, e);
     }
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
@@ -322,13 +297,16 @@ __global__ __launch_bounds__(WG) void gauss_reg_bwd_kernel(const T* __restrict__
         gmom[rw * 2 * CS + CS + rr] = (T)dl[k];
       }
     }
-  }
+  });
 }
 
-static inline long long blocks_for(long long total) {
+// ---- host side ----
+static inline long long blocks_capped(long long total, long long cap) {
   const long long tiles = (total + TILE - 1) / TILE;
-  return tiles < MAX_BLOCKS ? tiles : MAX_BLOCKS;
+  return tiles < cap ? tiles : cap;
 }
+static inline int blocks_for(long long total) { return (int)blocks_capped(total, MAX_BLOCKS); }      // forward: stage 2 reads them
+static inline int blocks_bwd(long long total) { return (int)blocks_capped(total, MAX_BLOCKS_BWD); }  // adjoints
 
 // element count of a shape, or <= 0 when it is malformed / beyond what the index arithmetic holds
 static inline long long shape_total(const cvvae_reduce_shape* s, bool two) {
@@ -342,6 +320,15 @@ static inline long long shape_total(const cvvae_reduce_shape* s, bool two) {
   if (s->L <= 0) return 0;
   if (s->L > (1LL << 40) / total) return -1;
   return total * s->L;
+}
+static inline int total_status(long long total) { return total == 0 ? CVVAE_EINVAL : (total < 0 ? CVVAE_EUNSUPPORTED : 0); }
+
+// the two operands' views of a shape
+struct Views {
+  View a, b;
+};
+static inline Views shape_views(const cvvae_reduce_shape* s) {
+  return {{s->n[1], s->n[2], s->L, s->sa[0], s->sa[1], s->sa[2]}, {s->n[1], s->n[2], s->L, s->sb[0], s->sb[1], s->sb[2]}};
 }
 
 static inline bool known_op(int32_t op) { return op >= CVVAE_RED_ABS_DIFF && op <= CVVAE_RED_SOFTPLUS_POS; }
@@ -380,7 +367,31 @@ static inline int frame_map_args(const cvvae_frame_map* fm, FrameMap* m, long lo
   *total = fm->rows * fm->frames_out * fm->HW;
   return 0;
 }
-static inline bool frames_op(int32_t op) { return two_operands(op); }
+
+// the Gaussian passes' extents -> 0 and the chunk / element counts, or the status to return; `pointers`: none of them is NULL
+static inline int gauss_args(bool pointers, int32_t dtype, int64_t B, int64_t C, int64_t S, long long* CS, long long* total) {
+  if (!pointers || B <= 0 || C <= 0 || S <= 0) return CVVAE_EINVAL;
+  if (!known_dtype(dtype)) return CVVAE_EUNSUPPORTED;
+  if (B >= (1 << 30) || C > (1LL << 40) / S || C * S > (1LL << 40) / B) return CVVAE_EUNSUPPORTED;
+  *CS = (long long)C * S;
+  *total = *CS * B;
+  return 0;
+}
+
+// f(TA tag, TB tag) for a pair of dtype codes
+template <typename F>
+static inline void by_dtypes(int32_t dtype_a, int32_t dtype_b, F&& f) {
+  by_dtype(dtype_a, [&](auto ta) { by_dtype(dtype_b, [&](auto tb) { f(ta, tb); }); });
+}
+
+// stage 1 through partials(nblk, ws), then stage 2: out = scale * the sum
+template <typename F>
+static inline int reduce_to(long long total, void* workspace, float scale, float* out, hipStream_t s, F&& partials) {
+  const int nblk = blocks_for(total);
+  partials(nblk, (float*)workspace);
+  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(WG), 0, s, (const float*)workspace, nblk, scale, out);
+  return launch_status();
+}
 
 }  // namespace loss
 }  // namespace cvvae
@@ -403,23 +414,18 @@ int cvvae_reduce_sum(int32_t op, int32_t dtype_a, const void* a, int32_t dtype_b
   const bool two = two_operands(op);
   if (two != (b != nullptr)) return CVVAE_EINVAL;
   const long long total = shape_total(shape, two);
-  if (total == 0) return CVVAE_EINVAL;
-  if (total < 0) return CVVAE_EUNSUPPORTED;
+  if (const int rc = total_status(total)) return rc;
   if (!b) dtype_b = CVVAE_F32;
-  const View va{shape->n[1], shape->n[2], shape->L, shape->sa[0], shape->sa[1], shape->sa[2]};
-  const View vb{shape->n[1], shape->n[2], shape->L, shape->sb[0], shape->sb[1], shape->sb[2]};
-  const int nblk = (int)blocks_for(total);
+  const Views v = shape_views(shape);
   hipStream_t s = (hipStream_t)stream;
-  by_dtype(dtype_a, [&](auto ta) {
-    by_dtype(dtype_b, [&](auto tb) {
+  return reduce_to(total, workspace, 1.0f, out, s, [&](int nblk, float* ws) {
+    by_dtypes(dtype_a, dtype_b, [&](auto ta, auto tb) {
       using TA = typename decltype(ta)::type;
       using TB = typename decltype(tb)::type;
-      hipLaunchKernelGGL((reduce_partial_kernel<TA, TB>), dim3(nblk), dim3(WG), 0, s, op, (const TA*)a, va, (const TB*)b, vb, total,
-                         (float*)workspace);
+      hipLaunchKernelGGL((reduce_partial_kernel<Strided<TA>, Strided<TB, true>>), dim3(nblk), dim3(WG), 0, s, op,
+                         Strided<TA>{(const TA*)a, v.a}, Strided<TB, true>{(const TB*)b, v.b}, total, ws);
     });
   });
-  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(WG), 0, s, (const float*)workspace, nblk, 1.0f, out);
-  return launch_status();
 }
 
 int cvvae_reduce_sum_bwd(int32_t op, int32_t dtype_a, const void* a, int32_t dtype_b, const void* b, const cvvae_reduce_shape* shape,
@@ -429,21 +435,14 @@ int cvvae_reduce_sum_bwd(int32_t op, int32_t dtype_a, const void* a, int32_t dty
   const bool two = two_operands(op);
   if (two != (b != nullptr) || (gb && !two)) return CVVAE_EINVAL;
   const long long total = shape_total(shape, two);
-  if (total == 0) return CVVAE_EINVAL;
-  if (total < 0) return CVVAE_EUNSUPPORTED;
+  if (const int rc = total_status(total)) return rc;
   if (!b) dtype_b = CVVAE_F32;
-  const View va{shape->n[1], shape->n[2], shape->L, shape->sa[0], shape->sa[1], shape->sa[2]};
-  const View vb{shape->n[1], shape->n[2], shape->L, shape->sb[0], shape->sb[1], shape->sb[2]};
-  const long long tiles = (total + TILE - 1) / TILE;
-  const int nblk = (int)(tiles < 65536 ? tiles : 65536);
-  hipStream_t s = (hipStream_t)stream;
-  by_dtype(dtype_a, [&](auto ta) {
-    by_dtype(dtype_b, [&](auto tb) {
-      using TA = typename decltype(ta)::type;
-      using TB = typename decltype(tb)::type;
-      hipLaunchKernelGGL((reduce_bwd_kernel<TA, TB>), dim3(nblk), dim3(WG), 0, s, op, (const TA*)a, va, (const TB*)b, vb, total, coef_dev,
-                         (TA*)ga, (TB*)gb);
-    });
+  const Views v = shape_views(shape);
+  by_dtypes(dtype_a, dtype_b, [&](auto ta, auto tb) {
+    using TA = typename decltype(ta)::type;
+    using TB = typename decltype(tb)::type;
+    hipLaunchKernelGGL((reduce_bwd_kernel<Strided<TA>, Strided<TB, true>>), dim3(blocks_bwd(total)), dim3(WG), 0, (hipStream_t)stream, op,
+                       Strided<TA>{(const TA*)a, v.a}, Strided<TB, true>{(const TB*)b, v.b}, total, coef_dev, (TA*)ga, (TB*)gb);
   });
   return launch_status();
 }
@@ -458,77 +457,58 @@ size_t cvvae_reduce_frames_workspace_bytes(const cvvae_frame_map* map) {
 int cvvae_reduce_sum_frames(int32_t op, int32_t dtype_a, const void* a, int32_t dtype_b, const void* clip, const cvvae_frame_map* map,
                             void* workspace, float* out, void* stream) {
   if (!a || !clip || !map || !workspace || !out) return CVVAE_EINVAL;
-  if (!frames_op(op) || !known_dtype(dtype_a) || !known_dtype(dtype_b)) return CVVAE_EUNSUPPORTED;
+  if (!two_operands(op) || !known_dtype(dtype_a) || !known_dtype(dtype_b)) return CVVAE_EUNSUPPORTED;
   FrameMap m{};
   long long total = 0;
-  const int rc = frame_map_args(map, &m, &total);
-  if (rc != 0) return rc;
-  const int nblk = (int)blocks_for(total);
+  if (const int rc = frame_map_args(map, &m, &total)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  by_dtype(dtype_a, [&](auto ta) {
-    by_dtype(dtype_b, [&](auto tb) {
+  return reduce_to(total, workspace, 1.0f, out, s, [&](int nblk, float* ws) {
+    by_dtypes(dtype_a, dtype_b, [&](auto ta, auto tb) {
       using TA = typename decltype(ta)::type;
       using TB = typename decltype(tb)::type;
-      hipLaunchKernelGGL((reduce_frames_partial_kernel<TA, TB>), dim3(nblk), dim3(WG), 0, s, op, (const TA*)a, (const TB*)clip, m, total,
-                         (float*)workspace);
+      hipLaunchKernelGGL((reduce_partial_kernel<Run<TA>, Frames<TB>>), dim3(nblk), dim3(WG), 0, s, op, Run<TA>{(const TA*)a},
+                         Frames<TB>{(const TB*)clip, m}, total, ws);
     });
   });
-  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(WG), 0, s, (const float*)workspace, nblk, 1.0f, out);
-  return launch_status();
 }
 
 int cvvae_reduce_sum_frames_bwd(int32_t op, int32_t dtype_a, const void* a, int32_t dtype_b, const void* clip, const cvvae_frame_map* map,
                                 const float* coef_dev, void* ga, void* stream) {
   if (!a || !clip || !map || !coef_dev || !ga) return CVVAE_EINVAL;
-  if (!frames_op(op) || !known_dtype(dtype_a) || !known_dtype(dtype_b)) return CVVAE_EUNSUPPORTED;
+  if (!two_operands(op) || !known_dtype(dtype_a) || !known_dtype(dtype_b)) return CVVAE_EUNSUPPORTED;
   FrameMap m{};
   long long total = 0;
-  const int rc = frame_map_args(map, &m, &total);
-  if (rc != 0) return rc;
-  const long long tiles = (total + TILE - 1) / TILE;
-  const int nblk = (int)(tiles < 65536 ? tiles : 65536);
-  hipStream_t s = (hipStream_t)stream;
-  by_dtype(dtype_a, [&](auto ta) {
-    by_dtype(dtype_b, [&](auto tb) {
-      using TA = typename decltype(ta)::type;
-      using TB = typename decltype(tb)::type;
-      hipLaunchKernelGGL((reduce_frames_bwd_kernel<TA, TB>), dim3(nblk), dim3(WG), 0, s, op, (const TA*)a, (const TB*)clip, m, total,
-                         coef_dev, (TA*)ga);
-    });
+  if (const int rc = frame_map_args(map, &m, &total)) return rc;
+  by_dtypes(dtype_a, dtype_b, [&](auto ta, auto tb) {
+    using TA = typename decltype(ta)::type;
+    using TB = typename decltype(tb)::type;
+    hipLaunchKernelGGL((reduce_bwd_kernel<Run<TA>, Frames<TB>>), dim3(blocks_bwd(total)), dim3(WG), 0, (hipStream_t)stream, op,
+                       Run<TA>{(const TA*)a}, Frames<TB>{(const TB*)clip, m}, total, coef_dev, (TA*)ga, (TB*)nullptr);
   });
   return launch_status();
 }
 
 int cvvae_gauss_reg(int32_t dtype, const void* moments, const void* noise, void* z, int64_t B, int64_t C, int64_t S, void* workspace,
                     float* kl_sum, void* stream) {
-  if (!moments || !z || !workspace || !kl_sum || B <= 0 || C <= 0 || S <= 0) return CVVAE_EINVAL;
-  if (!known_dtype(dtype)) return CVVAE_EUNSUPPORTED;
-  if (B >= (1 << 30) || C > (1LL << 40) / S || C * S > (1LL << 40) / B) return CVVAE_EUNSUPPORTED;
-  const long long CS = (long long)C * S, total = CS * B;
-  const int nblk = (int)blocks_for(total);
+  long long CS = 0, total = 0;
+  if (const int rc = gauss_args(moments && z && workspace && kl_sum, dtype, B, C, S, &CS, &total)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  by_dtype(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    hipLaunchKernelGGL(gauss_reg_kernel<T>, dim3(nblk), dim3(WG), 0, s, (const T*)moments, (const T*)noise, (T*)z, CS, total,
-                       (float*)workspace);
+  return reduce_to(total, workspace, 0.5f, kl_sum, s, [&](int nblk, float* ws) {
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(gauss_reg_kernel<T>, dim3(nblk), dim3(WG), 0, s, (const T*)moments, (const T*)noise, (T*)z, CS, total, ws);
+    });
   });
-  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(WG), 0, s, (const float*)workspace, nblk, 0.5f, kl_sum);
-  return launch_status();
 }
 
 int cvvae_gauss_reg_bwd(int32_t dtype, const void* moments, const void* noise, const void* g_z, const float* coef_kl_dev,
                         void* g_moments, int64_t B, int64_t C, int64_t S, void* stream) {
-  if (!moments || !coef_kl_dev || !g_moments || B <= 0 || C <= 0 || S <= 0) return CVVAE_EINVAL;
-  if (!known_dtype(dtype)) return CVVAE_EUNSUPPORTED;
-  if (B >= (1 << 30) || C > (1LL << 40) / S || C * S > (1LL << 40) / B) return CVVAE_EUNSUPPORTED;
-  const long long CS = (long long)C * S, total = CS * B;
-  const long long tiles = (total + TILE - 1) / TILE;
-  const int nblk = (int)(tiles < 65536 ? tiles : 65536);
-  hipStream_t s = (hipStream_t)stream;
+  long long CS = 0, total = 0;
+  if (const int rc = gauss_args(moments && coef_kl_dev && g_moments, dtype, B, C, S, &CS, &total)) return rc;
   by_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    hipLaunchKernelGGL(gauss_reg_bwd_kernel<T>, dim3(nblk), dim3(WG), 0, s, (const T*)moments, (const T*)noise, (const T*)g_z, coef_kl_dev,
-                       (T*)g_moments, CS, total);
+    hipLaunchKernelGGL(gauss_reg_bwd_kernel<T>, dim3(blocks_bwd(total)), dim3(WG), 0, (hipStream_t)stream, (const T*)moments,
+                       (const T*)noise, (const T*)g_z, coef_kl_dev, (T*)g_moments, CS, total);
   });
   return launch_status();
 }
