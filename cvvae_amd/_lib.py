@@ -174,6 +174,8 @@ PROTOTYPES = {
     "cvvae_mt_adamw_master": (_i32, [_i32, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _vp, _vp]),
     "cvvae_mt_sumsq": (_i32, [_i32, _vp, _vp, _i64, _vp, _vp]),
     "cvvae_mt_norm_finish": (_i32, [_vp, _i64, _f32, _vp, _vp]),
+    "cvvae_mt_pack_wide": (_i32, [_i32, _vp, _vp, _i64, _f32, _vp]),
+    "cvvae_mt_adamw_master_wide": (_i32, [_i32, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _vp, _vp]),
     "cvvae_frame_metrics_workspace_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32, _i32]),
     "cvvae_frame_metrics": (_i32, [_vp, ctypes.POINTER(ClipView), _vp, ctypes.POINTER(ClipView), _i32, _i32, _i32, _i32, _i32, _i32,
                                    _vp, _vp, _vp, _vp, _vp]),

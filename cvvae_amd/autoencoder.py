@@ -105,7 +105,9 @@ class AbstractAutoencoder(nn.Module):
         `training_step` from now on exchanges the gradients between `manual_backward` and the clip through one
         `ddp.GradientSync(params of the optimizer, group, **sync_kwargs)` per optimizer, made on its first use.  `validation_step`
         then averages its logs over the group.  After `master_weights()` the fp32 seeds / masters are broadcast as well (the gradient
-        exchange is unchanged: 16-bit gradients keep their per-dtype torch path).  The train logs stay rank-local, the learning rate is not scaled by the group's size
+        exchange is unchanged: 16-bit gradients keep their per-dtype torch path, unless `wide_gradients=True` is passed: they are
+        then widened into fp32 slots of the bucket, summed over the ranks in fp32 and handed to the master AdamW pass in place as
+        `p.main_grad`; ValueError from the first `training_step` if the optimizer has no `master_weights`).  The train logs stay rank-local, the learning rate is not scaled by the group's size
         and the sampler is the caller's, as with the reference's `strategy: ddp` without `--scale_lr`.  Call it on every rank,
         before the first `training_step` (optimizer state is not broadcast)."""
         from . import ddp
@@ -128,6 +130,9 @@ class AbstractAutoencoder(nn.Module):
         sync = self._dp["syncs"].get(id(optimizer))
         if sync is None:
             from . import ddp
+            if self._dp["kwargs"].get("wide_gradients") and not getattr(optimizer, "master_weights", False):
+                raise ValueError("data_parallel(wide_gradients=True): the fp32 `main_grad` of a 16-bit parameter is read by "
+                                 "cvvae_amd.optim.AdamW(master_weights=True) alone; call engine.master_weights() first")
             sync = self._dp["syncs"][id(optimizer)] = ddp.GradientSync(
                 [p for g in optimizer.param_groups for p in g["params"]], self._dp["group"], **self._dp["kwargs"])
         return sync

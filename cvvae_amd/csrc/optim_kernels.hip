@@ -104,17 +104,20 @@ struct AdamW {
   float beta1, one_minus_beta1, beta2, one_minus_beta2, eps, decay;  // decay = 1 - lr weight_decay
 };
 
-// T: the storage type of g and p.  float: p itself is updated.  A 16-bit type: the fp32 weights are the master (the `shadow` field),
-// and p is rewritten as the new master rounded to nearest even.  One element update for both, so master, m and v come out with the
-// bits of the fp32 pass on fp32 copies (tests/test_gpu_master_optim.py); tests/test_gpu_update_parity.py pins the bits themselves
-template <typename T>
+// T: the storage type of p.  float: p itself is updated.  A 16-bit type: the fp32 weights are the master (the `shadow` field),
+// and p is rewritten as the new master rounded to nearest even.  G: the storage type of g, T or float (a 16-bit parameter whose
+// gradient is its fp32 slot of the data-parallel bucket: cvvae_mt_adamw_master_wide).  One element update for all, so master, m and
+// v come out with the bits of the fp32 pass on fp32 copies (tests/test_gpu_master_optim.py, tests/test_gpu_ddp_wide.py);
+// tests/test_gpu_update_parity.py pins the bits themselves
+template <typename T, typename G = T>
 __global__ __launch_bounds__(WG) void adamw_kernel(const cvvae_mt_chunk* __restrict__ chunks, const cvvae_mt_tensor* __restrict__ tensors,
                                                    long long n_chunks, AdamW h, const float* __restrict__ coef_dev) {
+  static_assert(std::is_same<G, T>::value || std::is_same<G, float>::value, "the gradient is stored as the parameter or as fp32");
   constexpr bool kMaster = !std::is_same<T, float>::value;
   const float coef = coef_dev ? coef_dev[0] : 1.f;
   for_each_chunk(chunks, n_chunks, [&](long long, const cvvae_mt_chunk& ch) {
     const cvvae_mt_tensor t = tensors[ch.tensor];
-    const T* g = (const T*)t.g + ch.start;
+    const G* g = (const G*)t.g + ch.start;
     float* w = (float*)(kMaster ? t.shadow : t.p) + ch.start;
     float* m = (float*)t.m + ch.start;
     float* v = (float*)t.v + ch.start;
@@ -126,9 +129,9 @@ __global__ __launch_bounds__(WG) void adamw_kernel(const cvvae_mt_chunk* __restr
       ld8_n(v + i, n, fv);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
-        const float G = coef_dev ? coef * fg[k] : fg[k];
-        fm[k] = __builtin_fmaf(h.beta1, fm[k], h.one_minus_beta1 * G);
-        fv[k] = __builtin_fmaf(h.beta2, fv[k], h.one_minus_beta2 * (G * G));
+        const float cg = coef_dev ? coef * fg[k] : fg[k];
+        fm[k] = __builtin_fmaf(h.beta1, fm[k], h.one_minus_beta1 * cg);
+        fv[k] = __builtin_fmaf(h.beta2, fv[k], h.one_minus_beta2 * (cg * cg));
         const float denom = sqrtf(fv[k]) / t.bias2_sqrt + h.eps;
         fw[k] = fw[k] * h.decay - t.step_size * (fm[k] / denom);
       }
@@ -159,11 +162,13 @@ __global__ __launch_bounds__(WG) void ema_kernel(const cvvae_mt_chunk* __restric
 
 // shadow <- g / divisor (zeros for a tensor without a gradient: g NULL).  `/` is the correctly rounded fp32 division (hipcc's default;
 // the Makefile sets no fast-math flag), as in adamw_kernel.  g and shadow carry no __restrict__: they may be one address.
+// S: the storage type of g; the slot is fp32.  A 16-bit S is widened exactly, then divided in fp32 (cvvae_mt_pack_wide)
+template <typename S>
 __global__ __launch_bounds__(WG) void pack_kernel(const cvvae_mt_chunk* __restrict__ chunks, const cvvae_mt_tensor* __restrict__ tensors,
                                                   long long n_chunks, float divisor) {
   for_each_chunk(chunks, n_chunks, [&](long long, const cvvae_mt_chunk& ch) {
     const cvvae_mt_tensor t = tensors[ch.tensor];
-    const float* g = t.g ? (const float*)t.g + ch.start : nullptr;
+    const S* g = t.g ? (const S*)t.g + ch.start : nullptr;
     float* d = (float*)t.shadow + ch.start;
     for_each_group(ch, [&](int i, int n) __attribute__((always_inline)) {
       float f[VEC];
@@ -277,7 +282,22 @@ int cvvae_mt_ema(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_ten
 int cvvae_mt_pack(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float divisor,
                   void* stream) {
   if (!(divisor > 0.f) || !(divisor <= 3.402823466e38f)) return CVVAE_EINVAL;
-  return launch_list(fp32_only(dtype, pack_kernel), chunks, tensors, n_chunks, stream, divisor);
+  return launch_list(fp32_only(dtype, pack_kernel<float>), chunks, tensors, n_chunks, stream, divisor);
+}
+
+int cvvae_mt_pack_wide(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float divisor,
+                       void* stream) {
+  if (!(divisor > 0.f) || !(divisor <= 3.402823466e38f)) return CVVAE_EINVAL;
+  ListKernel<float> kernel = nullptr;
+  by_dtype16(dtype, [&](auto tag) { kernel = pack_kernel<typename decltype(tag)::type>; });
+  return launch_list(kernel, chunks, tensors, n_chunks, stream, divisor);
+}
+
+int cvvae_mt_adamw_master_wide(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, double lr,
+                               double beta1, double beta2, double eps, double weight_decay, const float* coef_dev, void* stream) {
+  ListKernel<AdamW, const float*> kernel = nullptr;
+  by_dtype16(dtype, [&](auto tag) { kernel = adamw_kernel<typename decltype(tag)::type, float>; });
+  return launch_adamw(kernel, chunks, tensors, n_chunks, lr, beta1, beta2, eps, weight_decay, coef_dev, stream);
 }
 
 }  // extern "C"

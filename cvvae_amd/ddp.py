@@ -27,6 +27,15 @@ sum_r(g_r / world) added in rank order, bit for bit, for any number of ranks (gl
 chunk from three ranks on).  It is a test and bring-up transport, not a fast one.  "auto": "device" for an `nccl` group, "host"
 otherwise.
 
+wide_gradients=True (off by default: nothing above changes).  A dense bf16 / fp16 parameter gets an fp32 slot of its element count
+under the same alignment rule; `slot_layout` is the same function.  sync() packs with one launch per source dtype present -- `ops.mt_pack`
+for the fp32 gradients, `ops.mt_pack_wide` (cvvae_mt_pack_wide: float(g) / world, widened exactly, divided in fp32) per 16-bit dtype --
+and reduces the bucket once: the ranks are summed in fp32, the all-reduce moves 4 bytes instead of 2 per 16-bit parameter.  torch
+refuses an fp32 `.grad` on a 16-bit parameter, so the averaged gradient of a 16-bit parameter is `p.main_grad` (the name Megatron and
+Apex use), the slot's view in the parameter's shape, and `p.grad` becomes None, which frees the 16-bit gradient; a 16-bit parameter
+without a gradient this iteration gets `main_grad = None` and a zeroed slot.  `cvvae_amd.optim.AdamW(master_weights=True)` reads
+`main_grad` in place (cvvae_mt_adamw_master_wide); no other optimizer does.  A 16-bit gradient the kernel cannot take keeps the torch path.
+
 bucket_bytes splits the buffer at slot boundaries into consecutive ranges, each all-reduced with async_op=True in order and all
 waited for before sync() returns.  The default, None, is ONE range: RCCL has not been measured on this path, so there is no tuned
 default to offer.  Overlapping the exchange with the backward is not attempted.
@@ -42,7 +51,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .optim import _kernel_tensor
+from .optim import _MASTER_DTYPES, _kernel_tensor
 
 __all__ = ["GradientSync", "slot_layout", "bucket_ranges", "all_reduce_sum", "broadcast", "world_size"]
 
@@ -117,7 +126,8 @@ NONE, KERNEL, TORCH = 0, 1, 2  # the agreement map's entries
 
 
 class GradientSync:
-    def __init__(self, params, group=None, transport: str = "auto", bucket_bytes: Optional[int] = None, check_first: int = 4):
+    def __init__(self, params, group=None, transport: str = "auto", bucket_bytes: Optional[int] = None, check_first: int = 4,
+                 wide_gradients: bool = False):
         self.params: List[torch.Tensor] = list(params)
         if len({id(p) for p in self.params}) != len(self.params):
             raise ValueError("GradientSync: a parameter is listed twice")
@@ -130,12 +140,15 @@ class GradientSync:
         self.transport = transport
         self.check_first = int(check_first)
         self.calls = 0
-        self.numels = [p.numel() if p.dtype == torch.float32 else 0 for p in self.params]
+        self.wide_gradients = bool(wide_gradients)
+        self.slot_dtypes = (torch.float32,) + (_MASTER_DTYPES if self.wide_gradients else ())   # parameter dtypes that have a slot
+        self.numels = [p.numel() if p.dtype in self.slot_dtypes else 0 for p in self.params]
         self.offsets, self.total = slot_layout(self.numels)
         self.ranges = bucket_ranges(self.offsets, self.total, bucket_bytes)
         self.flat: Optional[torch.Tensor] = None      # the bucket, made on the first sync() that has a gradient for the kernel
         self.slots: List[torch.Tensor] = []           # per parameter: its slot as a view of the parameter's shape
-        self._mtl: Optional[ops.MultiTensorList] = None
+        self._mtl: Optional[ops.MultiTensorList] = None   # the fp32 gradients' pack list (a 16-bit parameter: no elements)
+        self._wide: list = []                         # wide_gradients: (16-bit dtype, parameter indices, its pack list) per dtype present
         self._host: Optional[torch.Tensor] = None     # transport "host": the pinned staging buffer
 
     def layout(self) -> List[int]:
@@ -145,14 +158,16 @@ class GradientSync:
     # ---- the bucket ----
     def _make(self, device: torch.device) -> None:
         self.flat = torch.zeros(self.total, dtype=torch.float32, device=device)   # the gaps are zero from here on
-        self.slots = [self.flat[o:o + n].view(p.shape if p.dtype == torch.float32 else (0,)) for p, o, n in zip(self.params, self.offsets, self.numels)]
-        self._mtl = ops.MultiTensorList(self.numels, device)
+        self.slots = [self.flat[o:o + n].view(p.shape if p.dtype in self.slot_dtypes else (0,)) for p, o, n in zip(self.params, self.offsets, self.numels)]
+        self._mtl = ops.MultiTensorList([n if p.dtype == torch.float32 else 0 for p, n in zip(self.params, self.numels)], device)
+        by = [(dt, [i for i, p in enumerate(self.params) if p.dtype == dt]) for dt in self.slot_dtypes[1:]]
+        self._wide = [(dt, sel, ops.MultiTensorList([self.numels[i] for i in sel], device, dt)) for dt, sel in by if sel]
         if self.transport == "host" and device.type != "cpu":
             self._host = torch.empty(self.total, dtype=torch.float32, pin_memory=True)
 
     def _takes(self, i: int, g: torch.Tensor) -> bool:
         p = self.params[i]
-        return (self.numels[i] == g.numel() and g.shape == p.shape and _kernel_tensor(g)
+        return (self.numels[i] == g.numel() and g.shape == p.shape and p.dtype in self.slot_dtypes and _kernel_tensor(g, (p.dtype,))
                 and (self.flat is None or g.device == self.flat.device))
 
     def _all_reduce(self, t: torch.Tensor, ranges) -> None:
@@ -218,13 +233,29 @@ class GradientSync:
         if self.flat is not None:
             # every call packs every slot (zeros where there is no gradient for the kernel): the buffer's content never depends on an
             # earlier iteration, and all ranks reduce the same ranges whatever their maps were
-            mtl = self._mtl.set(g=[g if c == KERNEL else None for g, c in zip(grads, codes)], shadow=self.slots)
-            ops.mt_pack(mtl, float(self.world))
-            mtl.release("g")
+            if self._mtl.n_chunks:              # (none: a list of 16-bit parameters alone under wide_gradients)
+                fp32 = [p.dtype == torch.float32 for p in self.params]
+                mtl = self._mtl.set(g=[g if c == KERNEL and f else None for g, c, f in zip(grads, codes, fp32)], shadow=self.slots)
+                ops.mt_pack(mtl, float(self.world))
+                mtl.release("g")
+            for dt, sel, mtl in self._wide:     # one more launch per 16-bit dtype present: float(g) / world into the fp32 slots
+                mtl.set(g=[grads[i] if codes[i] == KERNEL else None for i in sel], shadow=[self.slots[i] for i in sel])
+                ops.mt_pack_wide(mtl, float(self.world))
+                mtl.release("g")
             self._exchange(self.flat, self.ranges, self._host)
             for p, c, s in zip(self.params, codes, self.slots):
-                if c == KERNEL:
-                    p.grad = s
+                if p.dtype == torch.float32:
+                    if c == KERNEL:
+                        p.grad = s
+                elif self.wide_gradients and p.dtype in _MASTER_DTYPES:
+                    # an fp32 .grad on a 16-bit parameter is refused by torch: the slot is `main_grad`, the 16-bit gradient is freed
+                    p.main_grad = s if c == KERNEL else None
+                    if c == KERNEL:
+                        p.grad = None
+        elif self.wide_gradients:
+            for p in self.params:      # no bucket yet (no gradient for the kernels so far): nothing stale may stay
+                if p.dtype in _MASTER_DTYPES:
+                    p.main_grad = None
         rest = {}
         for g, c in zip(grads, codes):
             if c == TORCH:

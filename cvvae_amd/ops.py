@@ -1647,6 +1647,14 @@ def mt_adamw_master(mtl: MultiTensorList, lr: float, beta1: float, beta2: float,
     _mt_adamw("cvvae_mt_adamw_master", ("g", "p", "m", "v", "shadow"), mtl, lr, beta1, beta2, eps, weight_decay, coef)
 
 
+def mt_adamw_master_wide(mtl: MultiTensorList, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
+                         coef: Optional[torch.Tensor] = None) -> None:
+    """mt_adamw_master for 16-bit parameters whose gradients are fp32 (include/cvvae.h cvvae_mt_adamw_master_wide): mtl.dtype (bf16 or
+    fp16) is the type of p alone; g -- the parameter's slot of the data-parallel bucket (cvvae_amd/ddp.py, `main_grad`) -- is fp32 like
+    m, v and the masters.  The same element update: the bits of mt_adamw on fp32 copies"""
+    _mt_adamw("cvvae_mt_adamw_master_wide", ("g", "p", "m", "v", "shadow"), mtl, lr, beta1, beta2, eps, weight_decay, coef)
+
+
 def mt_sumsq(mtl: MultiTensorList, partials: torch.Tensor) -> None:
     """the first stage of mt_grad_norm for a list of any float dtype (include/cvvae.h cvvae_mt_sumsq): one fp32 partial per chunk into
     partials[0, n_chunks), an fp32 DEVICE tensor -- usually a slice of the workspace that the lists of one mixed-dtype norm share"""
@@ -1680,3 +1688,9 @@ def mt_pack(mtl: MultiTensorList, divisor: float) -> None:
     """shadow <- g / divisor over the list (include/cvvae.h cvvae_mt_pack): the gradients into their slots of the bucket that the
     data-parallel exchange all-reduces (cvvae_amd/ddp.py), zeros where the list's g entry is None.  A correctly rounded fp32 division"""
     _mt_pass("cvvae_mt_pack", mtl, ("g", "shadow"), lambda lib: (float(divisor),))
+
+
+def mt_pack_wide(mtl: MultiTensorList, divisor: float) -> None:
+    """mt_pack for 16-bit gradients (include/cvvae.h cvvae_mt_pack_wide): mtl.dtype (bf16 or fp16) is the type of g alone, shadow the
+    fp32 slots: shadow <- float(g) / divisor, widened exactly and divided in fp32, zeros where the list's g entry is None"""
+    _mt_pass("cvvae_mt_pack_wide", mtl, ("g", "shadow"), lambda lib: (float(divisor),))

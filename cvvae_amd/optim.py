@@ -26,7 +26,14 @@ of 4e-5 (half an ulp is 3.9e-3): torch's step on such a group rounds every updat
 same pass, the fp32 tensors of the same group go through cvvae_mt_adamw, and `max_grad_norm` reduces ONE norm over the mixed list
 (cvvae_mt_sumsq per dtype, fp32 partials first, cvvae_mt_norm_finish).  `master(p)` looks a master up.  state_dict() carries the
 fp32 state; load_state_dict() keeps it fp32 (torch's would cast it to the parameter's dtype), takes a plain torch.optim.AdamW state
-(moments upcast, master = p) and then writes p <- round(master): the optimizer state is the source of truth."""
+(moments upcast, master = p) and then writes p <- round(master): the optimizer state is the source of truth.
+
+fp32 gradients of 16-bit parameters: under `ddp.GradientSync(wide_gradients=True)` a 16-bit parameter's averaged gradient is
+`p.main_grad`, its fp32 slot of the data-parallel bucket, and `p.grad` is None.  With `master_weights=True` a 16-bit parameter whose
+`main_grad` is a dense fp32 device tensor of its shape has that as its gradient wherever step() looks for `p.grad`: the norm reads it
+with the fp32 instance in the parameter's place among the partials (at world size 1 the norm keeps its bits), the step makes one
+launch per (parameter dtype, gradient width) present -- cvvae_mt_adamw_master_wide for these -- and `zero_grad()` clears it.  A group
+that holds one and does not run on the kernels is an error.  Without `master_weights=True` the optimizer never reads `main_grad`."""
 import math
 from typing import Iterable, List, Optional, Union
 
@@ -43,6 +50,15 @@ _MASTER_STATE = ("exp_avg", "exp_avg_sq", "master")
 
 def _kernel_tensor(t: torch.Tensor, dtypes=(torch.float32,)) -> bool:
     return t.is_cuda and t.dtype in dtypes and not t.is_sparse and t.is_contiguous()
+
+
+def _main_grad(p: torch.Tensor) -> Optional[torch.Tensor]:
+    """the fp32 gradient of a 16-bit parameter that the data-parallel exchange left in its bucket (cvvae_amd/ddp.py
+    GradientSync(wide_gradients=True): `p.main_grad`), when it is a dense fp32 device tensor of p's shape; else None"""
+    g = getattr(p, "main_grad", None) if p.dtype in _MASTER_DTYPES else None
+    if torch.is_tensor(g) and g.shape == p.shape and g.device == p.device and _kernel_tensor(g):
+        return g
+    return None
 
 
 class _Lists:
@@ -99,17 +115,31 @@ class AdamW(torch.optim.AdamW):
         self.__dict__.setdefault("_seeds", {})
         self._lists = _Lists()
 
+    def _grad(self, p: torch.Tensor) -> Optional[torch.Tensor]:
+        """the gradient step() reads for p: `p.grad`; with master_weights, the fp32 `p.main_grad` of a 16-bit parameter where set"""
+        g = _main_grad(p) if self.master_weights else None
+        return g if g is not None else p.grad
+
+    def zero_grad(self, set_to_none: bool = True) -> None:
+        super().zero_grad(set_to_none)
+        if self.master_weights:
+            for group in self.param_groups:
+                for p in group["params"]:
+                    if getattr(p, "main_grad", None) is not None:
+                        p.main_grad = None    # a view of the data-parallel bucket: nothing to free, the next sync() sets it again
+
     def _on_kernels(self, group) -> bool:
         if group.get("fused") or any(group.get(k) for k in _NO_KERNEL) or torch.is_tensor(group["lr"]):
             return False
         seen, dtypes = None, self._dtypes()
         for p in group["params"]:
-            g = p.grad
+            g = self._grad(p)
             if g is None:
                 continue
             if g.is_sparse:
                 raise RuntimeError("Adam does not support sparse gradients, please consider SparseAdam instead")
-            if not (_kernel_tensor(p, dtypes) and _kernel_tensor(g, (p.dtype,)) and g.device == p.device and seen in (None, p.device)):
+            width = (p.dtype,) if g is p.grad else (torch.float32,)
+            if not (_kernel_tensor(p, dtypes) and _kernel_tensor(g, width) and g.device == p.device and seen in (None, p.device)):
                 return False
             seen = p.device
         return seen is not None
@@ -124,9 +154,9 @@ class AdamW(torch.optim.AdamW):
         on_kernels = [self._on_kernels(g) for g in groups]
         coef = None
         if self.max_grad_norm is not None:
-            with_grad = [p for g in groups for p in g["params"] if p.grad is not None]
+            with_grad = [p for g in groups for p in g["params"] if self._grad(p) is not None]
             devices = {p.device for p in with_grad}
-            if with_grad and len(devices) == 1 and all(k or not any(p.grad is not None for p in g["params"]) for k, g in zip(on_kernels, groups)):
+            if with_grad and len(devices) == 1 and all(k or not any(self._grad(p) is not None for p in g["params"]) for k, g in zip(on_kernels, groups)):
                 out2 = self._norm(with_grad)
                 self.last_grad_norm, coef = out2[0], out2[1]
             elif with_grad:
@@ -135,13 +165,18 @@ class AdamW(torch.optim.AdamW):
         for group, k in zip(groups, on_kernels):
             if k:
                 self._kernel_step(group, coef)
+            elif any(self._grad(p) is not p.grad for p in group["params"]):
+                raise RuntimeError("cvvae_amd.optim.AdamW: a parameter of this group has an fp32 main_grad, which only the kernels "
+                                   "read, and the group does not run on them (see the module's docstring for what does)")
             elif any(p.grad is not None for p in group["params"]):
                 self._torch_step(group)
         return loss
 
     def _norm(self, with_grad):
         """-> the device tensor [norm, coef] over the gradients of `with_grad`: one launch pair for an fp32 list; for a mixed one a
-        partial per chunk of each dtype's list side by side in one workspace (fp32 first, then bf16, then fp16) and one merge"""
+        partial per chunk of each dtype's list side by side in one workspace (fp32 first, then bf16, then fp16) and one merge.  The
+        partials are laid out by the PARAMETER's dtype; a 16-bit parameter's fp32 `main_grad` is read by the fp32 instance in its
+        parameter's place (the same chunks, squares and sums as float(g16)), after the 16-bit gradients of its dtype if both occur"""
         by_dtype = [(dt, [p for p in with_grad if p.dtype == dt]) for dt in self._dtypes()]
         by_dtype = [(dt, ps) for dt, ps in by_dtype if ps]
         if [dt for dt, _ in by_dtype] == [torch.float32]:
@@ -149,7 +184,13 @@ class AdamW(torch.optim.AdamW):
             out2 = ops.mt_grad_norm(mtl, self.max_grad_norm)
             mtl.release("g")
             return out2
-        lists = [self._lists.get("norm", ps, dt).set(g=[p.grad for p in ps]) for dt, ps in by_dtype]
+        lists = []
+        for dt, ps in by_dtype:
+            wide = [self._grad(p) is not p.grad for p in ps]
+            for w, tag, width in ((False, "norm", dt), (True, ("norm-wide", dt), torch.float32)):
+                sel = [p for p, f in zip(ps, wide) if f == w]
+                if sel:
+                    lists.append(self._lists.get(tag, sel, width).set(g=[self._grad(p) for p in sel]))
         partials = torch.empty(sum(m.n_chunks for m in lists), dtype=torch.float32, device=with_grad[0].device)
         at = 0
         for m in lists:
@@ -191,15 +232,33 @@ class AdamW(torch.optim.AdamW):
         return st
 
     def _kernel_step(self, group, coef):
+        wide = {}     # 16-bit parameter -> its fp32 main_grad
         for p in group["params"]:
-            if p.grad is not None and p.dtype in _MASTER_DTYPES:
+            g = self._grad(p)
+            if g is not None and p.dtype in _MASTER_DTYPES:
                 self._master_state(p)
+                if g is not p.grad:
+                    wide[p] = g
         params: List[torch.Tensor] = []
         grads: List[torch.Tensor] = []
         exp_avgs: List[torch.Tensor] = []
         exp_avg_sqs: List[torch.Tensor] = []
         steps: List[torch.Tensor] = []
         self._init_group(group, params, grads, exp_avgs, exp_avg_sqs, [], steps)   # torch's own lazy state
+        if wide:
+            # torch collects the parameters that have a .grad: main_grad replaces that of one listed, the others (.grad is None after
+            # the exchange) join with the state _master_state made
+            listed = {p: i for i, p in enumerate(params)}
+            for p, g in wide.items():
+                if p in listed:
+                    grads[listed[p]] = g
+                    continue
+                st = self.state[p]
+                params.append(p)
+                grads.append(g)
+                exp_avgs.append(st["exp_avg"])
+                exp_avg_sqs.append(st["exp_avg_sq"])
+                steps.append(st["step"])
         torch._foreach_add_(steps, 1)
         beta1, beta2 = (float(b) for b in group["betas"])
         lr = float(group["lr"])
@@ -207,17 +266,17 @@ class AdamW(torch.optim.AdamW):
         step_size = [lr / (1.0 - beta1 ** s) for s in t]
         bias2_sqrt = [math.sqrt(1.0 - beta2 ** s) for s in t]
         hyper = (lr, beta1, beta2, float(group["eps"]), float(group["weight_decay"]), coef)
-        for dt in self._dtypes():
-            sel = [i for i, p in enumerate(params) if p.dtype == dt]
+        for dt, w in [(dt, w) for dt in self._dtypes() for w in (False, True)]:      # one launch per (parameter dtype, gradient width)
+            sel = [i for i, p in enumerate(params) if p.dtype == dt and (p in wide) == w]
             if not sel:
                 continue
             pick = lambda xs: [xs[i] for i in sel]  # noqa: E731
             fields = dict(g=pick(grads), p=pick(params), m=pick(exp_avgs), v=pick(exp_avg_sqs))
             if dt != torch.float32:
                 fields["shadow"] = [self.state[p]["master"] for p in fields["p"]]
-            mtl = self._lists.get(id(group["params"]), fields["p"], dt)
+            mtl = self._lists.get((id(group["params"]), "wide") if w else id(group["params"]), fields["p"], dt)
             mtl.set(step_size=pick(step_size), bias2_sqrt=pick(bias2_sqrt), **fields)
-            (ops.mt_adamw if dt == torch.float32 else ops.mt_adamw_master)(mtl, *hyper)
+            (ops.mt_adamw if dt == torch.float32 else ops.mt_adamw_master_wide if w else ops.mt_adamw_master)(mtl, *hyper)
             mtl.release("g")
         # every other writer of a parameter moves its version counter: the weight caches, the autocast copies and grad3d's
         # forward / backward check key on it
@@ -265,13 +324,20 @@ def clip_grad_norm_(parameters: Union[torch.Tensor, Iterable[torch.Tensor]], max
     """torch.nn.utils.clip_grad_norm_ for norm_type 2 on the kernels: the gradients are scaled in place by min(1, max_norm / (norm +
     1e-6)) and the total norm comes back as a 0-dim device tensor; two sweeps, no host synchronisation.  Gradients that are not all
     dense contiguous fp32 tensors on one ROCm device, another norm_type or error_if_nonfinite (which has to look at the norm on the
-    host) go to torch's own function."""
+    host) go to torch's own function.  A 16-bit parameter whose fp32 `main_grad` is set (cvvae_amd/ddp.py GradientSync(wide_gradients=
+    True), the set-up of AdamW(master_weights=True)) has that as its gradient: it is fp32, so it runs on the kernels and is scaled in
+    its slot of the bucket; torch's function does not know `main_grad`, so what would send such a list there is an error."""
     if isinstance(parameters, torch.Tensor):
         parameters = [parameters]
-    ps = [p for p in parameters if p.grad is not None]
-    grads = [p.grad for p in ps]
+    parameters = list(parameters)
+    wide = {p: _main_grad(p) for p in parameters}
+    ps = [p for p in parameters if wide[p] is not None or p.grad is not None]
+    grads = [wide[p] if wide[p] is not None else p.grad for p in ps]
     if (not grads or float(norm_type) != 2.0 or error_if_nonfinite or len({g.device for g in grads}) != 1
             or not all(_kernel_tensor(g) for g in grads)):
+        if any(g is not None for g in wide.values()):
+            raise NotImplementedError("clip_grad_norm_: fp32 main_grads are clipped on the kernels alone: norm_type 2, no "
+                                      "error_if_nonfinite, every gradient a dense contiguous fp32 tensor on one ROCm device")
         return torch.nn.utils.clip_grad_norm_(ps, max_norm, norm_type, error_if_nonfinite, foreach)
     mtl = _clip_lists.get("clip", ps).set(g=grads)
     out2 = ops.mt_grad_norm(mtl, float(max_norm))

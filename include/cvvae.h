@@ -667,6 +667,19 @@ int cvvae_conv333_s2_dgrad_small(int32_t dtype, const void* gy, int64_t gy_pix_s
  * partials[0, n_chunks): the caller lays the lists' partials side by side in one workspace (fp32 list first, then the 16-bit ones) and
  * cvvae_mt_norm_finish merges all n_partials of them into out2 = {norm, coef} exactly as the second stage above (NaN included).  On an
  * fp32 list the pair gives the bits of cvvae_mt_grad_norm; on a 16-bit list the bits of the fp32 list of float(g).
+ *
+ * 16-bit gradients in the fp32 bucket of the data-parallel exchange (cvvae_amd/ddp.py GradientSync(wide_gradients=True); additions to
+ * ABI 14, cvvae_mt_pack and cvvae_mt_adamw_master keep their contracts):
+ * cvvae_mt_pack_wide (reads g; writes shadow): cvvae_mt_pack for 16-bit gradients.  dtype is CVVAE_BF16 or CVVAE_F16 and is the type of
+ * g ONLY; shadow is the tensor's fp32 slot:   shadow_i[k] = float(g_i[k]) / divisor,   +0 for a tensor whose g is NULL.  The widening
+ * is exact and the quotient the correctly rounded fp32 division of cvvae_mt_pack, so the slot holds the bits cvvae_mt_pack writes for
+ * the fp32 copy of g.  6 bytes per element.  2-byte alignment is enough for g, 4-byte for shadow; 16-byte vectors per operand where it
+ * is 16-byte aligned.  CVVAE_F32 and unknown dtypes: CVVAE_EUNSUPPORTED; the other argument checks are cvvae_mt_pack's.
+ * cvvae_mt_adamw_master_wide (reads g; updates master, m, v; writes p): cvvae_mt_adamw_master for a 16-bit parameter whose gradient is
+ * fp32 -- its slot of the bucket after the all-reduce, read in place.  dtype (CVVAE_BF16 or CVVAE_F16) is the type of p ONLY; g, m, v
+ * and the master (the `shadow` field) are fp32.  The arithmetic is cvvae_mt_adamw's: master, m and v get the bits cvvae_mt_adamw gives on
+ * fp32 copies fed the same g, and where g is exactly float(g16) all four outputs have the bits of cvvae_mt_adamw_master fed g16.
+ * 30 bytes per parameter against cvvae_mt_adamw_master's 28.  Dtype refusals and argument checks are cvvae_mt_adamw_master's.
  */
 #define CVVAE_MT_CHUNK 8192                 /* elements; a multiple of the loss kernels' 2048-element tile */
 #define CVVAE_MT_MAX_CHUNKS (1LL << 31)
@@ -700,6 +713,10 @@ int cvvae_mt_adamw_master(int32_t dtype, const cvvae_mt_chunk* chunks, const cvv
 int cvvae_mt_sumsq(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float* partials,
                    void* stream);
 int cvvae_mt_norm_finish(const float* partials, int64_t n_partials, float max_norm, float* out2, void* stream);
+int cvvae_mt_pack_wide(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, float divisor,
+                       void* stream);
+int cvvae_mt_adamw_master_wide(int32_t dtype, const cvvae_mt_chunk* chunks, const cvvae_mt_tensor* tensors, int64_t n_chunks, double lr,
+                               double beta1, double beta2, double eps, double weight_decay, const float* coef_dev, void* stream);
 
 /*
  * Per-frame reconstruction metrics of two clips on the 8-bit scale, data_range = 255 (cvvae_amd/metrics.py; csrc/metrics_kernels.hip):
