@@ -34,6 +34,7 @@
 
 #include "../../include/cvvae.h"
 #include "conv_kernel.h"
+#include "knobs.h"
 
 namespace cvvae {
 
@@ -663,24 +664,25 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   for (int e = threadIdx.x; e < nci * ntaps; e += 256) o[e] = sm[(e / ntaps) * pitch + e % ntaps];
 }
 
-// does the weight-gradient launch of this convolution also produce the bias gradient?  (wgrad_dma_kernel: 16-bit operands, 3x3 taps)
-static bool wgrad_fuses_bias(const cvvae_conv_desc* d) {
-  static const bool dma_off = getenv("CVVAE_WGRAD_DMA") && atoi(getenv("CVVAE_WGRAD_DMA")) == 0;
-  return !dma_off && d->dtype < CVVAE_F32 && d->kH == 3;
-}
+// does this launch run wgrad_dma_kernel?  (16-bit operands, 3x3 taps; CVVAE_WGRAD_DMA=0: the register-staged kernel for every layer --
+// A/B aid, read once.)  That kernel also produces the bias gradient, works one workgroup per CU and reads the zero page.
+static bool wgrad_uses_dma(const cvvae_conv_desc* d) { return knob_on<KNOB_WGRAD_DMA>() && d->dtype < CVVAE_F32 && d->kH == 3; }
 
-static void wgrad_plan(const cvvae_conv_desc* d, int& nslab, int& n_co, int& n_ci) {
-  n_co = (d->Cout + 127) / 128;
-  n_ci = (d->Cin + 63) / 64;
+// The slab split of a launch and the workspace it needs, as byte offsets: the partial tiles [nslab][taps][n_co x 128][n_ci x 64] fp32,
+// then the 512-byte zero page of wgrad_dma_kernel, then its per-slab bias sums [nslab][n_co x 128] fp32.
+// cvvae_conv_wgrad_workspace_bytes reserves `total`; the launch addresses the three parts by the same offsets.
+struct WgradWorkspace { int nslab, n_co, n_ci; long long part, zero, bias, total; };
+
+static WgradWorkspace wgrad_workspace(const cvvae_conv_desc* d) {
+  const int n_co = (d->Cout + 127) / 128, n_ci = (d->Cin + 63) / 64;
   const bool xp = d->dtype >= CVVAE_F32;
   const int kp = d->kH == 1 ? (xp ? 64 : 128) : (xp ? 32 : 64);      // the kernel's K panel (wgrad_kernel)
   const long long rows = (long long)d->B * d->To * d->Ho * ((d->Wo + kp - 1) / kp);  // panels in all
   const long long per_slab = (long long)n_co * n_ci * d->kT;
-  static const int target = getenv("CVVAE_WGRAD_WGS") ? atoi(getenv("CVVAE_WGRAD_WGS")) : 0;   // (tuning aid, read once)
-  static const bool dma_off = getenv("CVVAE_WGRAD_DMA") && atoi(getenv("CVVAE_WGRAD_DMA")) == 0;
+  const int target = knob_int<KNOB_WGRAD_WGS>();                      // (tuning aid, read once)
   long long s = (768 + per_slab - 1) / per_slab;                      // ~3 workgroups per CU in all
   if (target > 0) s = target >= 512 ? (target + per_slab - 1) / per_slab : target / per_slab;
-  else if (!xp && d->kH == 3 && !dma_off) {
+  else if (wgrad_uses_dma(d)) {
     // wgrad_dma_kernel: ONE workgroup per CU at a time (its LDS), the workgroups of a slab share an XCD (slab % 8), and every
     // workgroup pays a pipeline fill and a 295 KB partial-tile store the CU waits for -- all of them at once, against HBM.  So the
     // fewest ROUNDS r of 32 workgroups per XCD that fill >= 90 % of the r x 32 places with whole slabs: 128 -> 128 (6 members per
@@ -700,70 +702,67 @@ static void wgrad_plan(const cvvae_conv_desc* d, int& nslab, int& n_co, int& n_c
   if (s > cap) s = cap;
   if (s > rows) s = rows;
   if (s < 1) s = 1;
-  nslab = (int)s;
+  auto up256 = [](long long b) { return (b + 255) / 256 * 256; };
+  WgradWorkspace w{(int)s, n_co, n_ci, 0, 0, 0, 0};
+  w.zero = w.part + up256(w.nslab * tile_bytes);
+  w.bias = w.zero + 512;
+  w.total = w.bias + up256((long long)w.nslab * n_co * 128 * 4);
+  return w;
 }
 
-static long long wgrad_partial_bytes(const cvvae_conv_desc* d, int nslab, int n_co, int n_ci) {
-  const long long b = (long long)nslab * d->kT * d->kH * d->kW * n_co * 128 * n_ci * 64 * (long long)sizeof(float);
-  return (b + 255) / 256 * 256;
-}
+// one weight-gradient launch: the kernel's arguments and what the host decides about it
+struct WgradLaunch {
+  WgradArgs p;
+  unsigned grid;
+  bool dma, fast;  // wgrad_dma_kernel, and its scalar-base form of the wave-loads
+  void* zero;      // the zero page (dma)
+};
 
-template <typename T, int KHW, bool XP, int SW>
-static int wgrad_launch_sw(const cvvae_conv_desc* d, const void* a, const void* gy, int64_t g_ps, float* dw, float* db, void* ws, hipStream_t s) {
-  int nslab, n_co, n_ci;
-  wgrad_plan(d, nslab, n_co, n_ci);
-  WgradArgs p{};
-  p.a = a; p.g = gy; p.part = (float*)ws; p.bias_part = nullptr;
+static WgradLaunch wgrad_launch_of(const cvvae_conv_desc* d, const void* a, const void* gy, int64_t g_ps, bool want_bias, void* ws) {
+  const WgradWorkspace w = wgrad_workspace(d);
+  char* base = reinterpret_cast<char*>(ws);
+  WgradLaunch L{};
+  WgradArgs& p = L.p;
+  p.a = a; p.g = gy; p.part = reinterpret_cast<float*>(base + w.part); p.bias_part = nullptr;
   p.B = d->B; p.Ti = d->Ti; p.Hi = d->Hi; p.Wi = d->Wi; p.Cin = d->Cin; p.a_ps = d->in_pix_stride;
   p.To = d->To; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout; p.g_ps = g_ps;
   p.kT = d->kT; p.sT = d->sT; p.sH = d->sH; p.sW = d->sW; p.pt = d->pad_t; p.ph = d->pad_h; p.pw = d->pad_w;
   p.mode_t = d->pad_mode_t; p.mode_hw = d->pad_mode_hw;
-  p.nslab = nslab; p.rows_total = d->B * d->To * d->Ho; p.n_ci_blk = n_ci;
-  p.Coutp = n_co * 128; p.Cinp = n_ci * 64;
-  p.n_coci = n_co * n_ci;
-  p.n_members = n_co * n_ci * d->kT;
-  const int nslab8 = (nslab + 7) / 8 * 8;  // (blocks of the padding slabs exit at once)
-  int rc = 0;
-  if (db && !wgrad_fuses_bias(d)) return CVVAE_EUNSUPPORTED;
-  // CVVAE_WGRAD_DMA=0: the register-staged kernel for every layer (A/B aid; read once)
-  static const bool dma_off = getenv("CVVAE_WGRAD_DMA") && atoi(getenv("CVVAE_WGRAD_DMA")) == 0;
-  if constexpr (KHW == 3 && !XP) {
-    if (!dma_off) {
-      // the zero page behind the partial tiles (cvvae_conv_wgrad_workspace_bytes reserves it)
-      char* zero = reinterpret_cast<char*>(ws) + wgrad_partial_bytes(d, nslab, n_co, n_ci);
-      if (db) p.bias_part = reinterpret_cast<float*>(zero + 512);   // [nslab][Coutp] behind the zero page
-      // the scalar-base form of the wave-loads (FAST, see the kernel): whole gradient panels, every channel of the tiles stored, the
-      // input tensor and the zero page inside one 4 GB window
-      const unsigned long long a0 = (unsigned long long)(size_t)a, z0 = (unsigned long long)(size_t)zero;
-      const unsigned long long a1 = a0 + (unsigned long long)d->B * d->Ti * d->Hi * d->Wi * d->in_pix_stride * sizeof(T);
-      const bool needs_zero = d->pad_mode_hw == 0 || d->pad_mode_t == 0;   // (else the zero page is never read: see the kernel)
-      const unsigned long long lo = !needs_zero || a0 < z0 ? a0 : z0, hi = !needs_zero || a1 > z0 + 512 ? a1 : z0 + 512;
-      const char* fenv = getenv("CVVAE_WGRAD_FAST");   // (read per call: tests compare the two address forms inside one process)
-      const bool fast_off = fenv && atoi(fenv) == 0;
-      const bool fast = !fast_off && d->Wo % 64 == 0 && d->in_pix_stride >= (long long)n_ci * 64 && g_ps >= (long long)n_co * 128 &&
-                        hi - lo < (1ull << 32) && (long long)d->Wo * g_ps * (long long)sizeof(T) < (1ll << 31);
+  p.nslab = w.nslab; p.rows_total = d->B * d->To * d->Ho; p.n_ci_blk = w.n_ci;
+  p.Coutp = w.n_co * 128; p.Cinp = w.n_ci * 64; p.n_coci = w.n_co * w.n_ci; p.n_members = w.n_co * w.n_ci * d->kT;
+  L.grid = (unsigned)((w.nslab + 7) / 8 * 8 * p.n_members);  // (blocks of the padding slabs exit at once)
+  L.dma = wgrad_uses_dma(d);
+  if (!L.dma) return L;
+  char* zero = base + w.zero; L.zero = zero;
+  if (want_bias) p.bias_part = reinterpret_cast<float*>(base + w.bias);
+  // the scalar-base form of the wave-loads (FAST, see the kernel): whole gradient panels, every channel of the tiles stored, the
+  // input tensor and the zero page inside one 4 GB window  (16-bit operands: two bytes per element)
+  const unsigned long long a0 = (unsigned long long)(size_t)a, z0 = (unsigned long long)(size_t)zero;
+  const unsigned long long a1 = a0 + (unsigned long long)d->B * d->Ti * d->Hi * d->Wi * d->in_pix_stride * 2;
+  const bool needs_zero = d->pad_mode_hw == 0 || d->pad_mode_t == 0;   // (else the zero page is never read: see the kernel)
+  const unsigned long long lo = !needs_zero || a0 < z0 ? a0 : z0, hi = !needs_zero || a1 > z0 + 512 ? a1 : z0 + 512;
+  // (CVVAE_WGRAD_FAST=0 is read per call: tests compare the two address forms inside one process)
+  L.fast = knob_on<KNOB_WGRAD_FAST>() && d->Wo % 64 == 0 && d->in_pix_stride >= (long long)w.n_ci * 64 && g_ps >= (long long)w.n_co * 128 &&
+           hi - lo < (1ull << 32) && (long long)d->Wo * g_ps * 2 < (1ll << 31);
+  return L;
+}
+
+template <typename T, int KHW, bool XP, int SW>
+static void wgrad_enqueue_sw(const WgradLaunch& L, hipStream_t s) {
+  if constexpr (KHW == 3 && !XP)
+    if (L.dma) {
       // (a form that keeps the input rows in LDS across consecutive output rows -- column-major panels, one new row per panel, 25.6 instead
       //  of 44 KB of wave-loads -- was built and measured 1-3 % slower: commit aa16cd7, profiles/r5_ab_wgrad_rounds.log)
-      if (fast) hipLaunchKernelGGL((wgrad_dma_kernel<T, SW, true>), dim3((unsigned)(nslab8 * p.n_members)), dim3(512), 0, s, p, (void*)zero);
-      else hipLaunchKernelGGL((wgrad_dma_kernel<T, SW, false>), dim3((unsigned)(nslab8 * p.n_members)), dim3(512), 0, s, p, (void*)zero);
-    } else {
-      hipLaunchKernelGGL((wgrad_kernel<T, KHW, XP, SW>), dim3((unsigned)(nslab8 * p.n_members)), dim3(512), 0, s, p);
+      if (L.fast) hipLaunchKernelGGL((wgrad_dma_kernel<T, SW, true>), dim3(L.grid), dim3(512), 0, s, L.p, L.zero);
+      else hipLaunchKernelGGL((wgrad_dma_kernel<T, SW, false>), dim3(L.grid), dim3(512), 0, s, L.p, L.zero);
+      return;
     }
-  } else {
-    hipLaunchKernelGGL((wgrad_kernel<T, KHW, XP, SW>), dim3((unsigned)(nslab8 * p.n_members)), dim3(512), 0, s, p);
-  }
-  rc = (int)hipGetLastError();
-  if (rc) return rc;
-  const int ntaps = d->kT * d->kH * d->kW;
-  if (ntaps > WGRAD_RED_MAXTAPS) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(p.Coutp * n_ci + (p.bias_part ? (d->Cout + 255) / 256 : 0))), dim3(256), 0, s,
-                     (const float*)ws, nslab, ntaps, p.Coutp, p.Cinp, d->Cout, d->Cin, dw, (const float*)p.bias_part, db);
-  return (int)hipGetLastError();
+  hipLaunchKernelGGL((wgrad_kernel<T, KHW, XP, SW>), dim3(L.grid), dim3(512), 0, s, L.p);
 }
 
 template <typename T, int KHW, bool XP>
-static int wgrad_launch(const cvvae_conv_desc* d, const void* a, const void* gy, int64_t g_ps, float* dw, float* db, void* ws, hipStream_t s) {
-  return d->sW == 2 ? wgrad_launch_sw<T, KHW, XP, 2>(d, a, gy, g_ps, dw, db, ws, s) : wgrad_launch_sw<T, KHW, XP, 1>(d, a, gy, g_ps, dw, db, ws, s);
+static void wgrad_enqueue(const WgradLaunch& L, hipStream_t s) {
+  L.p.sW == 2 ? wgrad_enqueue_sw<T, KHW, XP, 2>(L, s) : wgrad_enqueue_sw<T, KHW, XP, 1>(L, s);
 }
 
 }  // namespace cvvae
@@ -774,16 +773,10 @@ extern "C" {
 
 int64_t cvvae_conv_wgrad_workspace_bytes(const cvvae_conv_desc* d) {
   if (!d || d->Cout <= 0 || d->Cin <= 0 || d->kT <= 0) return CVVAE_EINVAL;
-  int nslab, n_co, n_ci;
-  wgrad_plan(d, nslab, n_co, n_ci);
-  // + the zero page of wgrad_dma_kernel + its per-slab bias sums
-  return (int64_t)wgrad_partial_bytes(d, nslab, n_co, n_ci) + 512 + ((int64_t)nslab * n_co * 128 * 4 + 255) / 256 * 256;
+  return (int64_t)wgrad_workspace(d).total;
 }
 
-int cvvae_conv_wgrad_fuses_bias(const cvvae_conv_desc* d) {
-  if (!d) return CVVAE_EINVAL;
-  return wgrad_fuses_bias(d) ? 1 : 0;
-}
+int cvvae_conv_wgrad_fuses_bias(const cvvae_conv_desc* d) { return !d ? CVVAE_EINVAL : (wgrad_uses_dma(d) ? 1 : 0); }
 
 int cvvae_conv_wgrad(const cvvae_conv_desc* d, const void* a, const void* gy, int64_t gy_pix_stride, float* dw, void* workspace,
                      void* stream_) {
@@ -800,17 +793,22 @@ int cvvae_conv_wgrad_bias(const cvvae_conv_desc* d, const void* a, const void* g
   if (d->upsample2x || d->in_overlap) return CVVAE_EUNSUPPORTED;
   if (!(d->kH == d->kW && (d->kH == 3 || d->kH == 1) && (d->kT == 3 || d->kT == 1))) return CVVAE_EUNSUPPORTED;
   if (d->sT < 1 || d->sT > 2 || d->sH < 1 || d->sH > 2 || d->sW < 1 || d->sW > 2 || d->sH != d->sW) return CVVAE_EUNSUPPORTED;
+  if (d->dtype < CVVAE_F16 || d->dtype > CVVAE_F32Q6) return CVVAE_EINVAL;
+  if (dbias && !wgrad_uses_dma(d)) return CVVAE_EUNSUPPORTED;
+  const WgradLaunch L = wgrad_launch_of(d, a, gy, gy_pix_stride, dbias != nullptr, workspace);
   const bool k3 = d->kH == 3;
-  if (d->dtype == CVVAE_F32 || d->dtype == CVVAE_F32Q || d->dtype == CVVAE_F32Q6)
-    return k3 ? wgrad_launch<__bf16, 3, true>(d, a, gy, gy_pix_stride, dw, dbias, workspace, stream)
-              : wgrad_launch<__bf16, 1, true>(d, a, gy, gy_pix_stride, dw, dbias, workspace, stream);
-  int rc = CVVAE_EINVAL;
-  by_dtype16(d->dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    rc = k3 ? wgrad_launch<T, 3, false>(d, a, gy, gy_pix_stride, dw, dbias, workspace, stream)
-            : wgrad_launch<T, 1, false>(d, a, gy, gy_pix_stride, dw, dbias, workspace, stream);
-  });
-  return rc;
+  if (d->dtype >= CVVAE_F32) k3 ? wgrad_enqueue<__bf16, 3, true>(L, stream) : wgrad_enqueue<__bf16, 1, true>(L, stream);
+  else by_dtype16(d->dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      k3 ? wgrad_enqueue<T, 3, false>(L, stream) : wgrad_enqueue<T, 1, false>(L, stream);
+    });
+  if (int rc = (int)hipGetLastError()) return rc;
+  const WgradArgs& p = L.p;
+  static_assert(WGRAD_RED_MAXTAPS >= 27, "the reduce kernel holds every tap of a 3x3x3 kernel");
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(p.Coutp * p.n_ci_blk + (p.bias_part ? (d->Cout + 255) / 256 : 0))), dim3(256), 0,
+                     stream, (const float*)p.part, p.nslab, d->kT * d->kH * d->kW, p.Coutp, p.Cinp, d->Cout, d->Cin, dw,
+                     (const float*)p.bias_part, dbias);
+  return (int)hipGetLastError();
 }
 
 }  // extern "C"

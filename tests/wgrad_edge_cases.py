@@ -6,7 +6,7 @@ cvvae_amd/csrc/bwd_kernels.hip what tests/pass_edge_cases.py and tests/boundary_
 A case is data only.  A conv case names the edge it reaches and DECLARES the facts of the launch plan it depends on: the kernel,
 the slab count, the fewest and most K panels a slab multiplies, how many slabs start in the middle of an output row, which
 boundary a mid-row slab crosses, and whether the launch is eligible for the scalar-base wave-loads (FAST).  The host test reads
-the slab count from the library and fails when a declared fact no longer holds, so a change of wgrad_plan cannot quietly turn
+the slab count from the library and fails when a declared fact no longer holds, so a change of wgrad_workspace (the slab split) cannot quietly turn
 the deep-pipeline cases back into one-panel launches."""
 from dataclasses import dataclass
 from typing import List, Tuple
