@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void relu_kernel(const T* x, long long nvec, T
     float f[8];
     ld8<T>(x + v * 8, f);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = f[j] > 0.f ? f[j] : 0.f;
+    for (int j = 0; j < 8; ++j) f[j] = f[j] <= 0.f ? 0.f : f[j];  // (NaN stays NaN, as torch.relu's)
     st8<T>(out + v * 8, f);
   }
 }
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void maxpool2x2_kernel(const T* __restrict__ x
       float f[8];
       ld8<T>(x + ((n * H + 2 * yo + (d >> 1)) * W + 2 * xo + (d & 1)) * C + c0, f);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) m[j] = f[j] > m[j] ? f[j] : m[j];
+      for (int j = 0; j < 8; ++j) m[j] = (f[j] > m[j] || f[j] != f[j]) ? f[j] : m[j];  // (a NaN anywhere in the window wins, as ATen's)
     }
     st8<T>(out + v * 8, m);
   }
@@ -159,6 +159,16 @@ __device__ __forceinline__ float group_sum(float x) {
 
 constexpr float LPIPS_EPS = 1e-10f;
 
+// a x - b y to one rounding of the difference, and EXACTLY 0 for equal operands: p = round(b y) and its exact error ep = b y - p (one
+// fma), then (a x - p) - ep.  A plain `a * x - b * y` is contracted into one fma, which keeps the rounding error of the other product:
+// identical features then had a non-zero difference, hence a non-zero level value and gradients where the reference computes exact
+// zeros.  With equal operands fma(a, x, -p) is that same error ep (it is representable), and the difference is 0.
+__device__ __forceinline__ float diff_of_products(float a, float x, float b, float y) {
+  const float p = b * y;
+  const float ep = __builtin_fmaf(b, y, -p);
+  return __builtin_fmaf(a, x, -p) - ep;
+}
+
 template <typename T, int LP>
 __global__ __launch_bounds__(256) void lpips_head_kernel(const T* __restrict__ f0, const T* __restrict__ f1,
                                                          const float* __restrict__ w, long long HW, float* __restrict__ ws) {
@@ -188,7 +198,7 @@ __global__ __launch_bounds__(256) void lpips_head_kernel(const T* __restrict__ f
     float d = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float e = a[j] * i0 - b[j] * i1;
+      const float e = diff_of_products(a[j], i0, b[j], i1);
       d = __builtin_fmaf(wv[j] * e, e, d);
     }
     acc += d;  // (a pixel beyond HW contributes exactly 0)
@@ -247,7 +257,7 @@ __global__ __launch_bounds__(256) void lpips_head_bwd_kernel(const T* __restrict
     float we[8], d0 = 0.f, d1 = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      we[j] = wv[j] * (a[j] * i0 - b[j] * i1);
+      we[j] = wv[j] * diff_of_products(a[j], i0, b[j], i1);
       d0 = __builtin_fmaf(we[j], a[j], d0);
       d1 = __builtin_fmaf(we[j], b[j], d1);
     }

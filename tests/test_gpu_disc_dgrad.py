@@ -11,7 +11,9 @@ import os
 
 import pytest
 import torch
-import torch.nn.functional as F
+
+from lossnet_ref import dgrad_bound as _bound  # the reference and the bound live with the edge tests' references (tests/lossnet_ref.py)
+from lossnet_ref import dgrad_ref as _ref
 
 pytestmark = pytest.mark.gpu
 
@@ -24,25 +26,6 @@ def _log(line):
     if d and os.path.isdir(d):
         with open(os.path.join(d, "disc_dgrad_parity.txt"), "a") as f:
             f.write(line + "\n")
-
-
-def _ref(gy, w, in_shape):
-    """fp64 autograd: gy [B,To,Ho,Wo,Cout], w [Cout,Cin,3,3,3] -> [B,T,H,W,Cin]"""
-    B, T, H, W = in_shape
-    x = torch.zeros(B, w.shape[1], T, H, W, dtype=torch.float64, requires_grad=True)
-    y = F.conv3d(x, w.double(), None, stride=2, padding=1)
-    assert tuple(y.shape[2:]) == tuple(gy.shape[1:4])
-    (y * gy.double().permute(0, 4, 1, 2, 3)).sum().backward()
-    return x.grad.permute(0, 2, 3, 4, 1)
-
-
-def _bound(ref, terms, dtype, cout):
-    acc = 8 * cout * 2.0 ** -24 * terms
-    if dtype == torch.float32:
-        return acc
-    fi = torch.finfo(dtype)
-    e = torch.floor(torch.log2((ref.abs() + acc).clamp_min(fi.tiny)))      # binade of the result (subnormals: the smallest normal's)
-    return acc + 0.5 * fi.eps * torch.exp2(e)
 
 
 def _operands(dtype, cout, in_shape, seed):
